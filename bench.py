@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: RHSoperator::Mult on the 3-D p=3 cylinder workloads.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload argon_p3|cfg2|cfg3|cfg5|torch6]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload argon_p3|cfg2|cfg3|cfg5|torch6] [--full]
+                    [--dump-outputs DIR]
 
 A "step" is one ``Mult`` (one explicit DG right-hand-side evaluation) over state resident in HBM.
 The mesh of the 3-D workloads is the 28x112x16 = 50 176-hex O-grid cylinder of BASELINE.json
@@ -22,7 +23,6 @@ configs[1]/[2] per GPU.  Workloads:
                   cfg5; torch6_mix: the same mixture with the argon mixture transport
   lte_torch       the table gas of the reference's LTE torch inputs (plasma.lte1d.ini: fluid = lte_table, one-dimensional
                   tables, radiation sink, viscosity-multiplier function), 5 equations, on the same mesh
-At N = 1 the JSON line also carries the workloads that were not selected, under `other_workloads`.
   cfg4            configs[3]: perfect-gas Navier-Stokes, p=3, on the 56x224x32 = 401 408-hex cylinder, cut into
                   N spanwise slabs (STRONG scaling: the total work is fixed)
 N > 1 (launched by ``torch.distributed.run``, one rank per GPU): every rank owns one block -- spanwise slabs of an
@@ -33,6 +33,13 @@ exchange).  ``--backend gloo --share-gpu`` rehearses the same launches on a one-
 (traces staged via host); the line then says so.  A failing exchange ends the run with a non-zero exit code.
 
 Prints ONE JSON line (rank 0).  ``value`` = DOFs of x processed per second by the whole job / 1e6.
+
+With --full the run also measures what the headline figure does not need: the RK4 time loop of the selected
+workload (`time_loop`), at N = 1 the workloads that were not selected (`other_workloads`, unless
+--no-other-workloads) and the CPU baseline (`cpu_baseline`, unless --no-cpu-baseline), at N > 1 the exposed
+communication (`comm_exposed_ms`).  A plain run sets up, warms up, times the K steps and prints the line.
+--dump-outputs DIR writes the right-hand side y of the last timed step as DIR/y.npy (float64, equations x nodes;
+above 56 MiB a fixed, seeded sample of nodes, whose indices are in DIR/y_nodes.npy; rank 0's block at N > 1).
 """
 import argparse
 import json
@@ -195,6 +202,28 @@ def cpu_baseline(neq, order, sample_case, budget_s=10.0):
                               "evals_per_s_on_sample": one["evals_per_s_on_sample"]}}
 
 
+DUMP_BYTES = 56 << 20  # --dump-outputs: at most this much in all (y and, when sampled, its node indices)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, y, neq, ndofs):
+    """y of the last timed step as out_dir/y.npy (float64, equations x nodes, the layout of x).  Larger than DUMP_BYTES:
+    every equation at a fixed, seeded sample of nodes (depends on the number of nodes only), indices in y_nodes.npy."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    yv = y.view(neq, ndofs)
+    if 8 * neq * ndofs <= DUMP_BYTES:
+        np.save(os.path.join(out_dir, "y.npy"), yv.cpu().numpy())
+        return
+    m = DUMP_BYTES // (8 * (neq + 1))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(ndofs, m, replace=False))
+    sample = yv.index_select(1, torch.from_numpy(idx).to(y.device))
+    np.save(os.path.join(out_dir, "y.npy"), sample.cpu().numpy())
+    np.save(os.path.join(out_dir, "y_nodes.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -208,10 +237,17 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo + --share-gpu rehearses the multi-rank path on a one-GPU box (traces staged via host)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: every rank uses device 0")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements the headline figure does not need: time_loop, other_workloads and "
+                         "cpu_baseline (N=1), comm_exposed_ms (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write y of the last timed step as DIR/y.npy (float64; a seeded node sample above 56 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full only: skip cpu_baseline")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="N=1 only: skip the secondary workloads reported under other_workloads")
+                    help="--full, N=1 only: skip the secondary workloads reported under other_workloads")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
 
     import numpy as np
     import torch
@@ -247,8 +283,9 @@ def main():
         if world > 1:
             dist.barrier()
 
-    def run(wname, steps, warmup):
-        """-> the JSON fields of one workload (rank 0; None elsewhere)"""
+    def run(wname, steps, warmup, full=False, dump_dir=None):
+        """-> the JSON fields of one workload (rank 0; None elsewhere); `full`: also the RK4 time loop (the selected
+        workload at N=1) and the exposed communication (N>1); `dump_dir`: write y of the last timed step there"""
         order, physics, make_bcs, make_state, description, sample_case = workload(wname)
         order = args.order or order
         axisym = wname in ("cfg5", "cfg5_const", "torch6", "torch6_mix", "lte_torch")
@@ -293,8 +330,10 @@ def main():
         mult_ms = sorted(op.mult_times())  # device time of each timed Mult (the last 128 at most)
         op.enable_kernel_timing(False)
         finite = bool(torch.isfinite(y).all().item())
+        if dump_dir and rank == 0:
+            dump_outputs(dump_dir, y, neq, ndofs)
         comm_exposed_ms = None
-        if world > 1 and halo is not None:
+        if full and world > 1 and halo is not None:
             # exposed communication: the same partitioned launches with the exchange switched off
             # (stale halo traces: timing only), max over ranks like the main number
             halo.skip = True
@@ -313,7 +352,7 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             comm_exposed_ms = 1e3 * (dt - float(t.item())) / steps
         rk4 = None
-        if world == 1 and wname == args.workload:
+        if full and world == 1 and wname == args.workload:
             # next row of the scope table: the RK4 time loop on the device (tpsrhs_advance),
             # a constant, tiny dt so that the state stays where the Mult timing left it
             nst = max(2, min(10, steps // 4))
@@ -396,9 +435,9 @@ def main():
         }
         return res, (neq, order, sample_case)
 
-    r = run(args.workload, args.steps, args.warmup)
+    r = run(args.workload, args.steps, args.warmup, full=args.full, dump_dir=args.dump_outputs)
     others = {}
-    if world == 1 and not args.no_other_workloads:
+    if args.full and world == 1 and not args.no_other_workloads:
         for wname in ("argon_p3", "cfg2", "cfg3", "cfg5", "cfg5_const", "torch6", "torch6_mix", "gll_dry", "lte_torch"):
             if wname != args.workload:
                 # the same K timed steps as the headline and at least 10 warm-ups: comparable round to round and
@@ -430,7 +469,7 @@ def main():
             out["comm_exposed_ms"] = res["comm_exposed_ms"]  # ms_per_step minus the same launches without the exchange
         if others:
             out["other_workloads"] = others
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(neq, order, sample_case)
         print(json.dumps(out))
     if world > 1:

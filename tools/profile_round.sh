@@ -7,10 +7,10 @@ W=${2:-argon_p3}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_${TAG}_${W}
 mkdir -p "$OUT"
-B="python3 bench.py --workload $W --steps 100 --warmup 10 --no-cpu-baseline --no-other-workloads"  # the default K and W of bench.py
+B="python3 bench.py --full --workload $W --steps 100 --warmup 10 --no-cpu-baseline --no-other-workloads"  # the default K and W of bench.py
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- $B > "$OUT/bench_traced.json" 2> "$OUT/trace.err"
 echo "trace done"
-P="python3 bench.py --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-other-workloads"
+P="python3 bench.py --full --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-other-workloads"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -- $P > /dev/null 2> "$OUT/pmc_fetch.err"
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -- $P > /dev/null 2> "$OUT/pmc_write.err"
 echo "hbm counters done"
