@@ -49,7 +49,12 @@ T *dev_alloc(size_t n) {
   T *p = nullptr;
   const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
   HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&p), bytes));
-  if (poison_allocations()) HIP_CHECK(hipMemset(p, 0xFF, bytes));
+  if (poison_allocations()) {
+    HIP_CHECK(hipMemset(p, 0xFF, bytes));
+    // the fill runs on the NULL stream, which is not ordered against a non-blocking stream (torch's side streams): it
+    // must be complete before the operator's stream first writes p (else a freshly zeroed NaN counter reads -1)
+    HIP_CHECK(hipDeviceSynchronize());
+  }
   return p;
 }
 template <class T>
