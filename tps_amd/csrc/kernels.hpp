@@ -50,6 +50,9 @@ namespace tpsrhs {
 #ifndef TPSRHS_ABLATE
 #define TPSRHS_ABLATE 0  // timing experiments only (wrong results)
 #endif
+#ifndef TPSRHS_LEAN_GENERAL
+#define TPSRHS_LEAN_GENERAL 0  // A/B switch: 1 = the one-hex lean face kernel (visc_phase_lean1, round 5) off, the general form everywhere
+#endif
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 
 // Diagnostic builds only (-DTPSRHS_STAMP=1, tools/stamp_phases.py): s_memtime at the phase boundaries of
@@ -1759,6 +1762,266 @@ __device__ inline void visc_phase_lean3d(const MeshDev &m, const int2 *sFI, type
     }
   }
 }
+// ---- the lean phase where the block is ONE hex whose lines fill whole rounds of the wave (p = 3; round 5).  Same stages,
+// same LDS layout and the same FP operations in the same order as visc_phase_lean3d; what differs is the integer work
+// around them, which was a fifth of the instructions the phase issued (profiles/r05_kgrad_census.txt):
+//   * the item loops of trace_lines / interp1_lines (signed item / LN, item % LN ... per trip, twelve line stages per hex)
+//     become compile-time rounds over offsets formed ONCE per face direction from the lane index (LeanLane);
+//   * the lanes beyond the TQ face points interpolate the last point again instead of being masked off: no zero / one
+//     initialisation of u, gv, gn for lanes whose values nobody reads, no exec juggling around the interpolation;
+//   * node_on is the same for every lane of a one-hex block: a scalar branch, and the in-flight nodal gradient needs no
+//     per-lane merge with zeros;
+//   * the 18 gradUp fields are read at (scalar field address) + (lane offset): the field address advances in SGPRs.
+template <class C>
+struct LeanLane {
+  unsigned lane;    // lane index, < BLOCK
+  unsigned tw;      // trace_lines: offset in T of item `lane` (field lane / LN, line lane % LN; round r adds r * FPR * TN)
+  unsigned ir, iw;  // interp1_lines: offsets in T and W of item `lane` (field, face, line jb)
+  unsigned pw, pb;  // interp2_point: offset in W (face, qa) and row of tab.B (qb) of face point min(lane, TQ - 1)
+  static constexpr int FPR = C::BLOCK / C::LN;  // fields per round of trace_lines
+  static_assert(C::EPB == 1 && C::DIM == 3 && C::BLOCK == 64 && C::BLOCK % C::LN == 0 && C::TQ <= C::BLOCK, "one hex per wave");
+  __device__ explicit LeanLane(unsigned t) : lane(t) {
+    tw = (t / C::LN) * C::TN + t % C::LN;
+    const unsigned fld = t / (C::PF * C::N1), r = t % (C::PF * C::N1), pf1 = r / C::N1, jb = r % C::N1;
+    ir = fld * C::TN + pf1 * C::NF + C::N1 * jb;
+    iw = fld * C::TW + pf1 * C::NW + jb;
+    const unsigned tq = t < C::TQ ? t : C::TQ - 1, pf = tq / C::NQ, q = tq - pf * C::NQ;
+    pw = pf * C::NW + (q % C::Q1) * C::N1;
+    pb = (q / C::Q1) * C::N1;
+  }
+  // trace_lines<C, D>: offset in a nodal array F[fld][NODES] of the first node of item `lane`'s line
+  template <int D>
+  __device__ unsigned trace_src() const {
+    const unsigned ln = lane % C::LN;
+    return (lane / C::LN) * C::NODES + (ln % C::N1) * stride_of<C>(tan_a<C>(D)) + (ln / C::N1) * stride_of<C>(tan_b<C>(D));
+  }
+};
+// trace_lines + interp1_lines of NFLD nodal fields F (src = LeanLane::trace_src<D>())
+template <class C, int D, int NFLD>
+__device__ inline void lean1_lines(const double *F, double *Tb, double *Wb, const Tables1D &ct, const LeanLane<C> &ll, unsigned src) {
+  constexpr int sd = stride_of<C>(D), FPR = LeanLane<C>::FPR, ROUNDS = (NFLD + FPR - 1) / FPR;
+  static_assert(NFLD * C::PF * C::N1 <= C::BLOCK, "interp1_lines: one round");
+#pragma unroll
+  for (int r = 0; r < ROUNDS; r++) {
+    if ((r + 1) * FPR <= NFLD || ll.lane < static_cast<unsigned>((NFLD - r * FPR) * C::LN)) {
+      const double *f = F + r * FPR * C::NODES + src;
+      double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+      for (int i = 0; i < C::N1; i++) {
+        const double v = ldsr(&f[i * sd]);
+        t0 += ct.b0[i] * v;
+        t1 += ct.b1[i] * v;
+      }
+      double *t = Tb + r * FPR * C::TN + ll.tw;
+      t[0] = t0;
+      t[C::NF] = t1;
+    }
+    // (one round at a time, like the trips of the loop this replaces: interleaved, the rounds' lines cost registers)
+    if (r + 1 < ROUNDS) __builtin_amdgcn_sched_barrier(0);
+  }
+  block_sync<C::BLOCK>();
+  if (ll.lane < static_cast<unsigned>(NFLD * C::PF * C::N1)) {
+    const double *t = Tb + ll.ir;
+    double v[C::N1];
+#pragma unroll
+    for (int ja = 0; ja < C::N1; ja++) v[ja] = ldsr(&t[ja]);
+    double *w = Wb + ll.iw;
+#pragma unroll
+    for (int qa = 0; qa < C::Q1; qa++) {
+      double acc = 0.0;
+#pragma unroll
+      for (int ja = 0; ja < C::N1; ja++) acc += ct.B[qa * C::N1 + ja] * v[ja];
+      w[qa * C::N1] = acc;
+    }
+  }
+  block_sync<C::BLOCK>();
+}
+// interp2_point of field k at this lane's face point
+template <class C>
+__device__ inline double lean1_point(const double *Wb, int k, const double *bq, const LeanLane<C> &ll) {
+  const double *w = Wb + k * C::TW + ll.pw;
+  double acc = 0.0;
+#pragma unroll
+  for (int jb = 0; jb < C::N1; jb++) acc += bq[jb] * ldsr(&w[jb]);
+  return acc;
+}
+// The nodal gradient of hex e0, one Cartesian direction (NEQ consecutive fields of gradUp) at a time, into the registers of
+// the node lanes.  The field address lives in an SGPR pair and advances by the field stride from load to load and from
+// direction to direction: the load takes it as its scalar base plus the 32-bit lane offset, and no 64-bit product is
+// formed (the compiler does those in VALU, per lane, even for uniform operands: the v_mad_u64_u32 of the general form).
+// Each address passes an empty asm as a scalar: left alone the compiler forms base + lane first and adds the strides per lane.
+// The element index is the same in every lane but arrives in a vector register when the block list is read from memory:
+// readfirstlane, and an empty asm so that the base is formed where it is used instead of being hoisted and held.
+template <class C>
+__device__ inline unsigned long long lean1_grad_base(const double *gradUp_q, int e0) {
+  unsigned es = __builtin_amdgcn_readfirstlane(e0);
+  asm volatile("" : "+s"(es));
+  return reinterpret_cast<unsigned long long>(gradUp_q) + static_cast<unsigned long long>(es) * (C::NPE * sizeof(double));
+}
+template <int NEQ>
+__device__ inline void lean1_issue_grad(unsigned long long &a, unsigned long long step, unsigned lane, double *gnext) {
+  typedef const double __attribute__((address_space(1))) *GP;
+#pragma unroll
+  for (int eq = 0; eq < NEQ; eq++) {
+    asm volatile("" : "+s"(a));
+    gnext[eq] = reinterpret_cast<GP>(a)[lane];
+    a += step;
+  }
+}
+template <class C, class PH, int D>
+__device__ inline void lean1_grad_dir(unsigned long long ga, unsigned long long gstep, bool node_on, double *gnext, double *sJ,
+                                      double *Tb, double *Wb, const Tab<C> &tab, const Tables1D &ct0, const double *n, double *gv,
+                                      double *gn, const LeanLane<C> &ll) {
+  constexpr int NEQ = PH::NEQ, DIM = C::DIM, NVEL = PH::NVEL;
+  const unsigned src = ll.template trace_src<D>();
+  auto stage = [&](auto ctag) {
+    constexpr int CD = decltype(ctag)::value;
+    if (node_on) {
+#pragma unroll
+      for (int eq = 0; eq < NEQ; eq++) sJ[eq * C::NODES + ll.lane] = gnext[eq];
+      if (CD + 1 < DIM) lean1_issue_grad<NEQ>(ga, gstep, ll.lane, gnext);
+    }
+    block_sync<C::BLOCK>();
+    const Tables1D &ct = fresh_table(ct0);
+    lean1_lines<C, D, NEQ>(sJ, Tb, Wb, ct, ll, src);
+    double bq[C::N1];
+#pragma unroll
+    for (int a = 0; a < C::N1; a++) bq[a] = tab.B[ll.pb + a];
+#pragma unroll
+    for (int k = 0; k < NEQ; k++) {
+      const double val = lean1_point<C>(Wb, k, bq, ll);
+      if (k >= 1 && k <= NVEL)
+        gv[(k - 1) + CD * DIM] = val;
+      else if (CD == 0)
+        gn[k] = 0.0 + n[CD] * val;  // (the sum starts from +0.0 as in lean_grad_chunk: same rounding, same sign of a zero)
+      else
+        gn[k] += n[CD] * val;
+    }
+    // (the sums end here: without the `if (tid < TQ)` region of the general form the compiler sinks them to their use, the
+    //  flux after the last stage, and lets the 24 operands of every stage wait in registers until then)
+#pragma unroll
+    for (int k = 0; k < NEQ; k++) {
+      if (k >= 1 && k <= NVEL)
+        asm volatile("" : "+v"(gv[(k - 1) + CD * DIM]));
+      else
+        asm volatile("" : "+v"(gn[k]));
+    }
+    block_sync<C::BLOCK>();
+  };
+  stage(std::integral_constant<int, 0>());
+  stage(std::integral_constant<int, 1>());
+  stage(std::integral_constant<int, 2>());
+}
+template <class C, class PH, int D>
+__device__ inline void lean1_state_dir(const double *sU, double *Tb, double *Wb, const Tab<C> &tab, const Tables1D &ct0, double *u,
+                                       const LeanLane<C> &ll) {
+  const Tables1D &ct = fresh_table(ct0);
+  lean1_lines<C, D, PH::NEQ>(sU, Tb, Wb, ct, ll, ll.template trace_src<D>());
+  double bq[C::N1];
+#pragma unroll
+  for (int a = 0; a < C::N1; a++) bq[a] = tab.B[ll.pb + a];
+#pragma unroll
+  for (int k = 0; k < PH::NEQ; k++) u[k] = lean1_point<C>(Wb, k, bq, ll);
+  block_sync<C::BLOCK>();
+}
+template <class C, class PH>
+__device__ inline void visc_phase_lean1(const MeshDev &m, const int2 *sFI, typename PH::PRef prm0, int e0, const double *sU,
+                                        const double *gradUp_q, bool node_on0, double *sJ, double *Tb, double *Wb,
+                                        const double *sV, const Tab<C> &tab, const Tables1D &ct, double *__restrict__ TB,
+                                        int tid0 STAMP_PARAM) {
+  constexpr int NEQ = PH::NEQ, DIM = C::DIM;
+  static_assert(DIM == 3 && C::Q_ROUNDS == 1 && PH::NVEL == 3 && C::BLOCK == 64 && C::EPB == 1, "3-D, one wave = one hex");
+  const bool node_on = __builtin_amdgcn_readfirstlane(node_on0) != 0;  // the same in every lane: a scalar branch
+#pragma clang loop unroll(disable)
+  for (int d = 0; d < DIM; d++) {
+    typename PH::PRef prm = PH::relaunder(prm0);  // the parameter loads of this direction stay inside it
+    // (the lane index through an empty asm: what is derived from it -- the six offsets of LeanLane, the face point -- is
+    //  formed once in the direction that uses it instead of being hoisted out of this loop and held, or spilled, across it)
+    int tid = tid0;
+    asm volatile("" : "+v"(tid));
+    const int pf = tid / C::NQ, q = tid - pf * C::NQ;
+    const int le = pf >> 1, s = pf & 1;
+    const bool on = tid < C::TQ && (e0 + le) < m.ne;
+    int nb = 0;
+    double n[DIM] = {1.0, 0.0, 0.0};
+    if (on) {
+      double wq, Xq[DIM];
+      nb = sFI[le * C::NFACES + 2 * d + s].x;
+      face_geometry_rt<C>(d, &sV[le * C::NV * DIM], tab, s, q, n, wq, Xq);
+    }
+    // 0: no viscous term on this face, 1: interior face, 2: wall face (interior state, then wall-side state)
+    const int np_lane = on ? PH::visc_passes(prm, nb) : 0;
+    const int npass = (__ballot(np_lane == 2) != 0) ? 2 : ((__ballot(np_lane >= 1) != 0) ? 1 : 0);
+    double *out = TB + static_cast<int64_t>((e0 + le) * C::NFACES + 2 * d + s) * ((NEQ - 1) * C::NQ) + q;
+    if (on && np_lane == 0) {
+#pragma unroll
+      for (int eq = 1; eq < NEQ; eq++) out[(eq - 1) * C::NQ] = 0.0;
+    }
+#pragma clang loop unroll(disable)
+    for (int pass = 0; pass < npass; pass++) {
+      double u[NEQ];
+      int tid1 = tid0;
+      asm volatile("" : "+v"(tid1));
+      const LeanLane<C> ll(static_cast<unsigned>(tid1) & (C::BLOCK - 1));
+      if (d == 0)
+        lean1_state_dir<C, PH, 0>(sU, Tb, Wb, tab, ct, u, ll);
+      else if (d == 1)
+        lean1_state_dir<C, PH, 1>(sU, Tb, Wb, tab, ct, u, ll);
+      else
+        lean1_state_dir<C, PH, 2>(sU, Tb, Wb, tab, ct, u, ll);
+      STAMP(5);
+      PH::clamp_species(u);
+      // the first Cartesian direction of the nodal gradient goes out before the closure (an L2 round trip behind ~1 500
+      // FP64 instructions), the others while their predecessor is interpolated
+      double gnext[NEQ];
+      unsigned long long ga = lean1_grad_base<C>(gradUp_q, e0);
+      const unsigned long long gstep = static_cast<unsigned long long>(m.ndofs) * sizeof(double);
+      if (node_on) {
+        lean1_issue_grad<NEQ>(ga, gstep, ll.lane, gnext);
+      } else {
+#pragma unroll
+        for (int eq = 0; eq < NEQ; eq++) gnext[eq] = 0.0;
+      }
+      typename PH::ViscLean cf;
+      if (pass < np_lane) {
+        typename PH::PRef pq = PH::relaunder(prm);
+        double Us[NEQ];
+        typename PH::WallFlux w;
+        PH::visc_pass_state(pq, nb, pass, u, n, Us, w);
+        PH::visc_point_lean(pq, Us, w, cf);
+      }
+      STAMP(6);
+      double gv[DIM * DIM], gn[NEQ];
+      if (d == 0)
+        lean1_grad_dir<C, PH, 0>(ga, gstep, node_on, gnext, sJ, Tb, Wb, tab, ct, n, gv, gn, ll);
+      else if (d == 1)
+        lean1_grad_dir<C, PH, 1>(ga, gstep, node_on, gnext, sJ, Tb, Wb, tab, ct, n, gv, gn, ll);
+      else
+        lean1_grad_dir<C, PH, 2>(ga, gstep, node_on, gnext, sJ, Tb, Wb, tab, ct, n, gv, gn, ll);
+      STAMP(7);
+      if (pass < np_lane) {
+        double f[NEQ];
+        PH::visc_normal_flux_lean(cf, gv, gn, n, f);
+        if (nb >= 0) {
+#pragma unroll
+          for (int eq = 1; eq < NEQ; eq++) {  // f[0] == 0 (src/fluxes.cpp:284)
+            if (TPSRHS_NT_STORES)
+              __builtin_nontemporal_store(f[eq], &out[(eq - 1) * C::NQ]);
+            else
+              out[(eq - 1) * C::NQ] = f[eq];
+          }
+        } else if (pass == 0) {  // wall face: -1/2 (Fv_in + Fv_wall) . n, the interior half first
+#pragma unroll
+          for (int eq = 1; eq < NEQ; eq++) out[(eq - 1) * C::NQ] = -0.5 * f[eq];
+        } else {
+#pragma unroll
+          for (int eq = 1; eq < NEQ; eq++) out[(eq - 1) * C::NQ] -= 0.5 * f[eq];
+        }
+      }
+      STAMP(8);
+    }
+  }
+}
 // 2-D viscous phase: both direction pairs at once (see Cfg::TQ2)
 template <class C, class PH>
 __device__ inline void visc_phase_2d(const MeshDev &m, const int2 *sFI, typename PH::PRef prm, int e0,
@@ -2031,7 +2294,10 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && PH::HEAVY) ? 1 : PH::minw_grad(
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       const double *gq = gradUp;
       const unsigned node = static_cast<unsigned>(e0 + le_n) * C::NPE + nd;
-      visc_phase_lean3d<C, PH>(m, sFI, prm, e0, sU, gq, node_on, node, sJ, sUp, sW, sV, tab, ct, TB, tid STAMP_ARG);
+      if constexpr (PH::LEAN_ONE_HEX && C::EPB == 1 && C::BLOCK % C::LN == 0 && !TPSRHS_ABLATE && !TPSRHS_LEAN_GENERAL)
+        visc_phase_lean1<C, PH>(m, sFI, prm, e0, sU, gq, node_on, sJ, sUp, sW, sV, tab, ct, TB, tid STAMP_ARG);
+      else
+        visc_phase_lean3d<C, PH>(m, sFI, prm, e0, sU, gq, node_on, node, sJ, sUp, sW, sV, tab, ct, TB, tid STAMP_ARG);
     }
     STAMP_FLUSH();
     return;

@@ -277,6 +277,10 @@ struct PlasmaPhys {
   // 12-18 values across the gradient interpolation instead of 38, the nodal gradient re-read from the L2 instead of held
   // in LDS -- 168 registers and 12 KB, THREE waves per SIMD (round 4; the collocated p <= 3 hexes, one wave per block).
   static constexpr bool LEAN_TRACE = (NSP_ == 3) && (DIM_ == 3);
+  // ... and of those, the single-temperature argon-minimal mixture (the metric's physics) runs the lean face kernel in its
+  // one-hex form where the block is one hex (kernels.hpp::visc_phase_lean1: lane offsets once per face direction, round 5).
+  // The other ternary instantiations keep the general form token for token: a third of them sit on the spill allow-list.
+  static constexpr bool LEAN_ONE_HEX = LEAN_TRACE && !TWOT && TRANSPORT == TRANSPORT_ARGON_MINIMAL;
   static constexpr bool LAUNDER_FLUX = false;  // k_flux re-fetches the parameter image where its face term starts (the table gas)
   static constexpr int minw_grad(int dim, int p, int nc) {
     return (LEAN_TRACE && dim == 3 && !nc && p <= 3) ? TPSRHS_PLASMA_MINW_GRAD_LEAN : MINW_GRAD;
