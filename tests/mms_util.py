@@ -151,6 +151,163 @@ def manufactured_ternary(X, lengths=(1.0, 1.0, 1.0)):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# Manufactured states that satisfy a boundary condition EXACTLY on planar patches (tests/test_mms_boundaries.py): the
+# weak boundary flux of such a state is consistent with the PDE, so the residual of the elements next to the patch
+# converges to the same exact right-hand side at the same order as the interior's.
+#   walls at y = 0 and y = L_y (x, z periodic):  s = sin(pi y / L_y) vanishes on both, c = cos(pi y / L_y) has
+#   a vanishing y-derivative on both;
+#   inlet at x = 0, outlet at x = L_x (y, z periodic):  a = sin(pi x / 2 L_x) vanishes at the inlet, b = cos(pi x / 2 L_x)
+#   at the outlet.
+# The data of the patches that go with the states:
+BC_WALL_TEMPERATURE = 300.0  # VISC_ISOTH
+BC_DRY_INLET = (1.2, 30.0, -12.0, 7.0)  # SUB_DENS_VEL: rho, u, v, w
+BC_DRY_OUTLET_PRESSURE = 101300.0  # SUB_P
+_TERNARY_M_AR, _TERNARY_M_E, _TERNARY_R_U = 39.948e-3, 5.4858e-7, 8.3144598
+_TERNARY_N_ION_IN, _TERNARY_N_B_IN, _TERNARY_T_REF = 2.0e-3, 1.4, 8000.0
+# SUB_DENS_VEL of the ternary: rho, u, v, w, rho Y_ion  (n_e = n_i: rho = m_Ar (n_i + n_B))
+BC_TERNARY_INLET = (_TERNARY_M_AR * (_TERNARY_N_ION_IN + _TERNARY_N_B_IN), 300.0, -100.0, 50.0,
+                    (_TERNARY_M_AR - _TERNARY_M_E) * _TERNARY_N_ION_IN)
+BC_TERNARY_OUTLET_PRESSURE = _TERNARY_R_U * (2 * _TERNARY_N_ION_IN + _TERNARY_N_B_IN) * _TERNARY_T_REF
+BC_KINDS = ("isoth", "adiab", "slip", "inout")
+
+
+def _dry_air_rhs(sp, X, rho, vel, p, viscous, visc_mult, bulk_mult):
+    """(U, -div(F_c - F_v)) of the primitives rho, vel, p: the closures of `_build`"""
+    dim = len(X)
+    T = p / (rho * RG)
+    E = p / (GAMMA - 1) + rho * sum(v * v for v in vel) / 2
+    U = [rho] + [rho * v for v in vel] + [E]
+    F = [[U[0] * vel[d] for d in range(dim)]]
+    for i in range(dim):
+        F.append([U[1 + i] * vel[d] + (p if i == d else 0) for d in range(dim)])
+    F.append([vel[d] * (E + p) for d in range(dim)])
+    if viscous:
+        mu = C1 * visc_mult * T ** sp.Rational(3, 2) / (T + S0)
+        mub = bulk_mult * mu - sp.Rational(2, 3) * mu
+        kap = mu * GAMMA * RG / ((GAMMA - 1) * PR)
+        div = sum(sp.diff(vel[d], X[d]) for d in range(dim))
+        tau = [[mu * (sp.diff(vel[i], X[j]) + sp.diff(vel[j], X[i])) + (mub * div if i == j else 0) for j in range(dim)]
+               for i in range(dim)]
+        for i in range(dim):
+            for d in range(dim):
+                F[1 + i][d] -= tau[i][d]
+        for d in range(dim):
+            F[dim + 1][d] -= sum(tau[i][d] * vel[i] for i in range(dim)) + kap * sp.diff(T, X[d])
+    return U, [-sum(sp.diff(F[eq][d], X[d]) for d in range(dim)) for eq in range(dim + 2)]
+
+
+@functools.lru_cache(maxsize=None)
+def _build_bc(dim, kind, viscous, visc_mult, bulk_mult, lengths):
+    """Dry air; kind:
+    "isoth"  every velocity component ~ s, T = T_w + (...) s, p free, rho = p / (R T): the VISC_ISOTH wall state;
+    "adiab"  velocities ~ s, T depends on y through c only (dT/dy = 0 on the walls): VISC_ADIAB;
+    "slip"   v ~ s, everything else mixes c and s so that nothing else vanishes on the walls: SLIP / INV with Euler;
+    "inout"  rho and the velocities leave their SUB_DENS_VEL data through a, p leaves its SUB_P datum through b."""
+    import sympy as sp
+
+    X = sp.symbols("x y z")[:dim]
+    k = [2 * sp.pi / L for L in lengths]
+    z3 = dim == 3
+    if kind == "inout":
+        a, b = sp.sin(sp.pi * X[0] / (2 * lengths[0])), sp.cos(sp.pi * X[0] / (2 * lengths[0]))
+        r0, u0, v0, w0 = BC_DRY_INLET
+        rho = r0 + 0.10 * a * sp.cos(k[1] * X[1]) + (0.05 * a * sp.sin(k[2] * X[2]) if z3 else 0)
+        vel = [u0 + 8.0 * a * sp.cos(k[1] * X[1] + 0.3) + (3.0 * a * sp.cos(k[2] * X[2]) if z3 else 0),
+               v0 + 6.0 * a * sp.sin(k[1] * X[1] + 0.5)]
+        if z3:
+            vel.append(w0 + 5.0 * a * sp.sin(k[2] * X[2] + 0.2) * sp.cos(k[1] * X[1]))
+        p = BC_DRY_OUTLET_PRESSURE * (1 + 0.04 * b * sp.sin(k[1] * X[1] - 0.4) + (0.02 * b * sp.cos(k[2] * X[2]) if z3 else 0))
+    else:
+        s, c = sp.sin(sp.pi * X[1] / lengths[1]), sp.cos(sp.pi * X[1] / lengths[1])
+        p = 101300.0 * (1 + 0.04 * sp.cos(k[0] * X[0] - 0.4) * (0.5 * c + 0.6 * s) + (0.02 * sp.cos(k[2] * X[2]) if z3 else 0))
+        if kind == "slip":
+            vel = [30.0 + 8.0 * sp.sin(k[0] * X[0] + 0.3) * (0.6 * c + 0.5 * s) + (3.0 * sp.cos(k[2] * X[2]) if z3 else 0),
+                   (-12.0 + 6.0 * sp.cos(k[0] * X[0])) * s]
+            if z3:
+                vel.append(7.0 + 5.0 * sp.sin(k[2] * X[2] + 0.2) * sp.cos(k[0] * X[0]) * (0.7 * c - 0.4 * s))
+            rho = 1.2 + 0.10 * sp.sin(k[0] * X[0]) * (0.7 * c + 0.4 * s) + (0.05 * sp.sin(k[2] * X[2]) if z3 else 0)
+        else:
+            vel = [(30.0 + 8.0 * sp.sin(k[0] * X[0] + 0.3) + (3.0 * sp.cos(k[2] * X[2]) if z3 else 0)) * s,
+                   (-12.0 + 6.0 * sp.cos(k[0] * X[0])) * s]
+            if z3:
+                vel.append((7.0 + 5.0 * sp.sin(k[2] * X[2] + 0.2) * sp.cos(k[0] * X[0])) * s)
+            if kind == "isoth":
+                T = BC_WALL_TEMPERATURE + (40.0 + 15.0 * sp.sin(k[0] * X[0]) + (8.0 * sp.sin(k[2] * X[2]) if z3 else 0)) * s
+            elif kind == "adiab":
+                T = 300.0 * (1 + 0.08 * sp.sin(k[0] * X[0]) * c + (0.03 * sp.sin(k[2] * X[2]) if z3 else 0))
+            else:
+                raise ValueError(kind)
+            rho = p / (RG * T)
+    U, rhs = _dry_air_rhs(sp, X, rho, vel, p, viscous, visc_mult, bulk_mult)
+    return sp.lambdify(X, U, "numpy"), sp.lambdify(X, rhs, "numpy")
+
+
+def manufactured_bc(X, kind, viscous=True, visc_mult=1.0, bulk_mult=0.0, lengths=(1.0, 1.0, 1.0)):
+    """X: node coordinates (dim, N) -> (U, exact dU/dt) of the dry-air state that satisfies the boundary condition `kind`"""
+    dim = X.shape[0]
+    fu, fr = _build_bc(dim, kind, bool(viscous), float(visc_mult), float(bulk_mult), tuple(lengths[:dim]))
+    bc = np.zeros(X.shape[1])
+    U = np.array([np.asarray(v, dtype=np.float64) + bc for v in fu(*X)])
+    R = np.array([np.asarray(v, dtype=np.float64) + bc for v in fr(*X)])
+    return U, R
+
+
+@functools.lru_cache(maxsize=None)
+def _build_ternary_bc(dim, kind, lengths):
+    """The closure of `_build_ternary` with kind = "slip" (inviscid walls at y = 0, L_y) or "inout" (rho, the velocities and
+    the ion partial density leave the SUB_DENS_VEL data through a, p its SUB_P datum through b, T from the equation of
+    state)."""
+    import sympy as sp
+
+    R_U, m_ar, m_e = _TERNARY_R_U, _TERNARY_M_AR, _TERNARY_M_E
+    e_form, cv = 1520571.3883, 1.5 * R_U
+    m_i = m_ar - m_e
+    X = sp.symbols("x y z")[:dim]
+    k = [2 * sp.pi / L for L in lengths]
+    z3 = dim == 3
+    if kind == "inout":
+        a, b = sp.sin(sp.pi * X[0] / (2 * lengths[0])), sp.cos(sp.pi * X[0] / (2 * lengths[0]))
+        r0, u0, v0, w0, ri0 = BC_TERNARY_INLET
+        rho = r0 * (1 + 0.08 * a * sp.cos(k[1] * X[1] + 0.2) + (0.04 * a * sp.sin(k[2] * X[2]) if z3 else 0))
+        ni = ri0 / m_i * (1 + 0.30 * a * sp.sin(k[1] * X[1] + 0.1))
+        vel = [u0 + 60.0 * a * sp.cos(k[1] * X[1] + 0.3), v0 + 40.0 * a * sp.sin(k[1] * X[1])]
+        if z3:
+            vel.append(w0 + 30.0 * a * sp.sin(k[2] * X[2] + 0.2) * sp.cos(k[1] * X[1]))
+        p = BC_TERNARY_OUTLET_PRESSURE * (1 + 0.10 * b * sp.sin(k[1] * X[1] - 0.4) + (0.03 * b * sp.cos(k[2] * X[2]) if z3 else 0))
+        nB = (rho - (m_i + m_e) * ni) / m_ar
+        T = p / (R_U * (2 * ni + nB))
+    elif kind == "slip":
+        s, c = sp.sin(sp.pi * X[1] / lengths[1]), sp.cos(sp.pi * X[1] / lengths[1])
+        T = _TERNARY_T_REF * (1 + 0.10 * sp.sin(k[0] * X[0]) * (0.6 * c + 0.5 * s))
+        nB = 1.4 * (1 + 0.08 * sp.cos(k[0] * X[0] + 0.2) * (0.5 * c + 0.6 * s) + (0.04 * sp.sin(k[2] * X[2]) if z3 else 0))
+        ni = 2.0e-3 * (1 + 0.30 * sp.sin(k[0] * X[0] - 0.5) * (0.7 * c + 0.4 * s))
+        vel = [300.0 + 60.0 * sp.sin(k[0] * X[0] + 0.3) * (0.6 * c + 0.5 * s), (-100.0 + 40.0 * sp.cos(k[0] * X[0])) * s]
+        if z3:
+            vel.append(50.0 + 30.0 * sp.sin(k[2] * X[2] + 0.2) * sp.cos(k[0] * X[0]) * (0.7 * c - 0.4 * s))
+        p = R_U * (2 * ni + nB) * T
+        rho = (m_i + m_e) * ni + m_ar * nB
+    else:
+        raise ValueError(kind)
+    E = cv * (2 * ni + nB) * T + e_form * ni + rho * sum(v * v for v in vel) / 2
+    U = [rho] + [rho * v for v in vel] + [E, m_i * ni]
+    rhs = [-sum(sp.diff(U[0] * vel[d], X[d]) for d in range(dim))]
+    for i in range(dim):
+        rhs.append(-sum(sp.diff(U[1 + i] * vel[d] + (p if i == d else 0), X[d]) for d in range(dim)))
+    rhs.append(-sum(sp.diff(vel[d] * (E + p), X[d]) for d in range(dim)))
+    rhs.append(-sum(sp.diff(m_i * ni * vel[d], X[d]) for d in range(dim)))
+    return sp.lambdify(X, U, "numpy"), sp.lambdify(X, rhs, "numpy")
+
+
+def manufactured_ternary_bc(X, kind, lengths=(1.0, 1.0, 1.0)):
+    dim = X.shape[0]
+    fu, fr = _build_ternary_bc(dim, kind, tuple(lengths[:dim]))
+    bc = np.zeros(X.shape[1])
+    U = np.array([np.asarray(v, dtype=np.float64) + bc for v in fu(*X)])
+    R = np.array([np.asarray(v, dtype=np.float64) + bc for v in fr(*X)])
+    return U, R
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # The reference's own manufactured-solution checks of ONE assembled Mult: utils/compute_rhs (utils/compute_rhs.cpp:
 # 102-160) behind test/mms.euler_2d.test and test/mms.cns_2d.test.  The exact state and its source come from MASA
 # [third party: pecos/MASA 0.50, absent from this image]; they are restated here from MASA's published forms and
