@@ -32,23 +32,9 @@
 
 namespace tpsrhs {
 
-#ifndef TPSRHS_MINW_GRAD
-#define TPSRHS_MINW_GRAD 1
-#endif
-#ifndef TPSRHS_MINW_FLUX
-#define TPSRHS_MINW_FLUX 3  // <= 168 VGPRs: 3 waves per SIMD (the allocator otherwise lands on 170)
-#endif
-#ifndef TPSRHS_NT_STORES
-#define TPSRHS_NT_STORES 0  // experiment: non-temporal stores of the streams k_gradient never reads back (Up, TB)
-#endif
+// (TPSRHS_MINW_GRAD / TPSRHS_MINW_FLUX, the launch-bound waves per SIMD: physics_dryair.hpp)
 #ifndef TPSRHS_NO_MFMA
 #define TPSRHS_NO_MFMA 0  // A/B switch: 1 = the dense inverse mass of the p = 3 Gauss-Lobatto hex on the vector ALU (rounds 2-3)
-#endif
-#ifndef TPSRHS_FLUX_LATE
-#define TPSRHS_FLUX_LATE 0  // experiment: k_flux issues the neighbour records of its first direction pair after the nodal physics
-#endif
-#ifndef TPSRHS_ABLATE
-#define TPSRHS_ABLATE 0  // timing experiments only (wrong results)
 #endif
 #ifndef TPSRHS_LEAN_GENERAL
 #define TPSRHS_LEAN_GENERAL 0  // A/B switch: 1 = the one-hex lean face kernel (visc_phase_lean1, round 5) off, the general form everywhere
@@ -307,26 +293,7 @@ __device__ inline EddyCtx closure_ctx(const MeshDev &m, bool dist_on, double dis
 // take one contiguous eighth of the block list, so that neighbours (all but those across the seven chunk borders) share
 // an L2.  A bijection of [0, n): XCD x runs the workgroups x, x + 8, ... -- q + (x < r) of them -- and owns the chunk
 // [x q + min(x, r), ...) of that length.
-#ifndef TPSRHS_GRAD_LATE
-#define TPSRHS_GRAD_LATE 1  // (0: A/B)
-#endif
-#ifndef TPSRHS_GRAD_LATE_NC
-#define TPSRHS_GRAD_LATE_NC 0  // (measured: gll_dry unchanged, 264 -> 244 registers notwithstanding)
-#endif
-// k_flux of the two-step (plasma) kernels: the nodal gradient (NEQ * DIM values per lane) is parked in the lane's own column
-// of the -- still unused -- flux region of the LDS pool while the state-only closure runs, instead of being held in
-// registers across it (A/B switch)
-#ifndef TPSRHS_FLUX_PARK_GRAD
-#define TPSRHS_FLUX_PARK_GRAD 0
-#endif
-#ifndef TPSRHS_GRAD_LATE_ALL
-#define TPSRHS_GRAD_LATE_ALL 0
-#endif
-#ifndef TPSRHS_XCD_ORDER
-#define TPSRHS_XCD_ORDER 1
-#endif
 __device__ inline int xcd_block(int b, int n, int reverse = 0) {
-#if TPSRHS_XCD_ORDER
   constexpr int X = 8;
   const int q = n / X, r = n - q * X;
   const int x = b % X, k = b / X;
@@ -335,9 +302,6 @@ __device__ inline int xcd_block(int b, int n, int reverse = 0) {
   // every sweep streaming 0.6 - 1 GB through a least-recently-used cache in the one order that never hits
   const int kk = reverse ? (q + (x < r ? 1 : 0)) - 1 - k : k;
   return x * q + (x < r ? x : r) + kk;
-#else
-  return reverse ? n - 1 - b : b;
-#endif
 }
 
 // Face records of the block's elements -> LDS, once, so that no later stage has a global load on the
@@ -500,10 +464,9 @@ __device__ inline void face_geometry(const double *V, const Tab<C> &tab, int s, 
 // traces on both faces of direction D of NFLD nodal fields F[fld][NODES]: one lane per line
 template <class C, int D, int NFLD>
 __device__ inline void trace_lines(const double *F, double *T, const Tables1D &ct, int tid) {
-  constexpr int DD = ((TPSRHS_ABLATE & 64) && C::DIM == 3 && D == 1) ? 2 : D;  // timing experiment: conflict-free pattern
-  constexpr int sd = stride_of<C>(DD);
-  constexpr int sa = stride_of<C>(tan_a<C>(DD));
-  constexpr int sb = (C::DIM == 3) ? stride_of<C>(tan_b<C>(DD)) : 0;
+  constexpr int sd = stride_of<C>(D);
+  constexpr int sa = stride_of<C>(tan_a<C>(D));
+  constexpr int sb = (C::DIM == 3) ? stride_of<C>(tan_b<C>(D)) : 0;
   for (int item = tid; item < NFLD * C::LN; item += C::BLOCK) {
     const int fld = item / C::LN, r = item - fld * C::LN;
     const int le = r / C::NF, ln = r - le * C::NF;
@@ -700,7 +663,7 @@ __device__ inline void issue_neighbour_traces(const int2 *sFI, const double *__r
       const int pf = item / C::NF, fn = item - pf * C::NF;
       const int2 fi = sFI[(pf >> 1) * C::NFACES + 2 * D + (pf & 1)];
       t.nb[r] = fi.x;
-      if (fi.x >= 0 && !(TPSRHS_ABLATE & 1)) {
+      if (fi.x >= 0) {
         const int pn = permute<C::DIM>(fi.y, C::N1, fn % C::N1, fn / C::N1);
         const double *src = TA + static_cast<int64_t>(fi.x) * rec + f0 * C::NF + pn;
 #pragma unroll
@@ -745,7 +708,7 @@ __device__ inline void issue_visc_traces(const int2 *sFI, int e0, const double *
       const int lslot = (pf >> 1) * C::NFACES + 2 * D + (pf & 1);
       const int2 fi = sFI[lslot];
       t.nb[r] = fi.x;
-      if (fi.x != INT32_MIN && !(TPSRHS_ABLATE & 1)) {
+      if (fi.x != INT32_MIN) {
         // the records hold equations 1 .. NEQ-1: the viscous flux of the continuity equation is zero
         const double *o = TB + (static_cast<int64_t>(e0) * C::NFACES + lslot) * ((NEQ - 1) * C::NQ) + q;
 #pragma unroll
@@ -1741,12 +1704,7 @@ __device__ inline void visc_phase_lean3d(const MeshDev &m, const int2 *sFI, type
         PH::visc_normal_flux_lean(cf, gv, gn, n, f);
         if (nb >= 0) {
 #pragma unroll
-          for (int eq = 1; eq < NEQ; eq++) {  // f[0] == 0 (src/fluxes.cpp:284)
-            if (TPSRHS_NT_STORES)
-              __builtin_nontemporal_store(f[eq], &out[(eq - 1) * C::NQ]);
-            else
-              out[(eq - 1) * C::NQ] = f[eq];
-          }
+          for (int eq = 1; eq < NEQ; eq++) out[(eq - 1) * C::NQ] = f[eq];  // f[0] == 0 (src/fluxes.cpp:284)
         } else if (pass == 0) {  // wall face: -1/2 (Fv_in + Fv_wall) . n, the interior half first
 #pragma unroll
           for (int eq = 1; eq < NEQ; eq++) out[(eq - 1) * C::NQ] = -0.5 * f[eq];
@@ -1756,9 +1714,6 @@ __device__ inline void visc_phase_lean3d(const MeshDev &m, const int2 *sFI, type
         }
       }
       STAMP(8);
-    }
-    if (on && npass == 0) {
-      // (np_lane == 0 for every lane: the zeros were written above)
     }
   }
 }
@@ -2004,12 +1959,7 @@ __device__ inline void visc_phase_lean1(const MeshDev &m, const int2 *sFI, typen
         PH::visc_normal_flux_lean(cf, gv, gn, n, f);
         if (nb >= 0) {
 #pragma unroll
-          for (int eq = 1; eq < NEQ; eq++) {  // f[0] == 0 (src/fluxes.cpp:284)
-            if (TPSRHS_NT_STORES)
-              __builtin_nontemporal_store(f[eq], &out[(eq - 1) * C::NQ]);
-            else
-              out[(eq - 1) * C::NQ] = f[eq];
-          }
+          for (int eq = 1; eq < NEQ; eq++) out[(eq - 1) * C::NQ] = f[eq];  // f[0] == 0 (src/fluxes.cpp:284)
         } else if (pass == 0) {  // wall face: -1/2 (Fv_in + Fv_wall) . n, the interior half first
 #pragma unroll
           for (int eq = 1; eq < NEQ; eq++) out[(eq - 1) * C::NQ] = -0.5 * f[eq];
@@ -2131,8 +2081,7 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && PH::HEAVY) ? 1 : PH::minw_grad(
   const int tid = threadIdx.x;
   const int lin = xcd_block(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x), m.reverse);
   const int bid = m.blocks ? m.blocks[lin] : lin;
-  // (TPSRHS_ABLATE & 512, timing experiment: every block works on one of 8 elements -- all loads become cache hits)
-  const int e0 = (TPSRHS_ABLATE & 512) ? (bid % 8) * C::EPB : bid * C::EPB;
+  const int e0 = bid * C::EPB;
   __shared__ int2 sFI[C::EPB * C::NFACES];
   STAMP_DECL;
   STAMP_START();
@@ -2158,7 +2107,7 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && PH::HEAVY) ? 1 : PH::minw_grad(
   // 127 / 128 at p = 4, 5) = FOUR waves per SIMD without a spill (round 2's 128-register cap cost 4 spilled registers).
   // Measured, alternating core libraries on one box (profiles/r04_ab_grad_late.txt): cfg2 k_gradient 0.400 -> 0.375 ms, the
   // Mult 0.823 -> 0.804.  The plasma kernels peak in their viscous phase (152 registers either way) and keep the early issue.
-  constexpr bool LATE = TPSRHS_GRAD_LATE && ((DIM == 3 && (!C::NC || TPSRHS_GRAD_LATE_NC) && !PH::HEAVY) || TPSRHS_GRAD_LATE_ALL);
+  constexpr bool LATE = DIM == 3 && !C::NC && !PH::HEAVY;
   issue_neighbour_traces<C, 0, NEQ>(sFI, TA, 2 * NEQ * C::NF, NEQ, ta0, tid);
   if (!LATE) {
     issue_neighbour_traces<C, 1, NEQ>(sFI, TA, 2 * NEQ * C::NF, NEQ, ta1, tid);
@@ -2174,10 +2123,7 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && PH::HEAVY) ? 1 : PH::minw_grad(
       sUp[eq * C::NODES + tid] = up[eq];
       // the Up grid function (a side effect Mult owns, src/rhs_operator.cpp:623-651) is written here: this
       // sweep is not bandwidth-bound, k_traces is
-      if (TPSRHS_NT_STORES)
-        __builtin_nontemporal_store(up[eq], &field_ptr(Upout, eq, m.ndofs)[n]);
-      else
-        field_ptr(Upout, eq, m.ndofs)[n] = up[eq];
+      field_ptr(Upout, eq, m.ndofs)[n] = up[eq];
     }
   }
   block_sync<C::BLOCK>();
@@ -2212,9 +2158,8 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && PH::HEAVY) ? 1 : PH::minw_grad(
       double dr[DIM];
 #pragma unroll
       for (int mm = 0; mm < DIM; mm++) {
-        const int m2 = ((TPSRHS_ABLATE & 128) && DIM == 3) ? 2 : mm;  // timing experiment
-        const int sd = stride_of<C>(m2);
-        const double *F = &sUp[eq * C::NODES + le_n * C::NPE + nd - idx[m2] * sd];
+        const int sd = stride_of<C>(mm);
+        const double *F = &sUp[eq * C::NODES + le_n * C::NPE + nd - idx[mm] * sd];
         double acc = 0.0;
 #pragma unroll
         for (int a = 0; a < C::N1; a++) acc += Dr[mm][a] * ldsr(&F[a * sd]);
@@ -2232,37 +2177,35 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && PH::HEAVY) ? 1 : PH::minw_grad(
 
   STAMP(2);
   // ---- face part of the gradient, collocated (grad_jump_nodal), one direction pair at a time
-  if (!(TPSRHS_ABLATE & 8)) {
-    // the jump of one direction pair: collocated (a product at the face nodes), or through the face quadrature
-    // points when nodes and points differ
-    auto jump = [&](auto dtag) {
-      constexpr int D = decltype(dtag)::value;
-      if constexpr (C::NC) {
-        nc_grad_jump<C, PH, D>(sFI, prm, sJ, pool + L::O_V, sV, tab, ct, node_on, le_n, idx, tid, g);
-      } else {
-        if (node_on) grad_jump_nodal<C, PH>(D, sFI, prm, sJ, sJ + NEQ * C::TN, sV, tab, le_n, idx, inv_mass, g);
-        block_sync<C::BLOCK>();
-      }
-    };
-    if (LATE) issue_neighbour_traces<C, 1, NEQ>(sFI, TA, 2 * NEQ * C::NF, NEQ, ta1, tid);
-    trace_lines<C, 0, NEQ>(sUp, sJ, ct, tid);
-    block_sync<C::BLOCK>();  // own traces complete (boundary faces copy them)
-    store_neighbour_traces<C, NEQ>(ta0, sJ, sJ + NEQ * C::TN, tid);
-    block_sync<C::BLOCK>();
-    jump(std::integral_constant<int, 0>());
-    if (LATE && DIM == 3) issue_neighbour_traces<C, (DIM == 3 ? 2 : 0), NEQ>(sFI, TA, 2 * NEQ * C::NF, NEQ, ta2, tid);
-    trace_lines<C, 1, NEQ>(sUp, sJ, ct, tid);
-    block_sync<C::BLOCK>();
-    store_neighbour_traces<C, NEQ>(ta1, sJ, sJ + NEQ * C::TN, tid);
-    block_sync<C::BLOCK>();
-    jump(std::integral_constant<int, 1>());
-    if (DIM == 3) {
-      trace_lines<C, (DIM == 3 ? 2 : 0), NEQ>(sUp, sJ, ct, tid);
+  // the jump of one direction pair: collocated (a product at the face nodes), or through the face quadrature
+  // points when nodes and points differ
+  auto jump = [&](auto dtag) {
+    constexpr int D = decltype(dtag)::value;
+    if constexpr (C::NC) {
+      nc_grad_jump<C, PH, D>(sFI, prm, sJ, pool + L::O_V, sV, tab, ct, node_on, le_n, idx, tid, g);
+    } else {
+      if (node_on) grad_jump_nodal<C, PH>(D, sFI, prm, sJ, sJ + NEQ * C::TN, sV, tab, le_n, idx, inv_mass, g);
       block_sync<C::BLOCK>();
-      store_neighbour_traces<C, NEQ>(ta2, sJ, sJ + NEQ * C::TN, tid);
-      block_sync<C::BLOCK>();
-      jump(std::integral_constant<int, (DIM == 3 ? 2 : 0)>());
     }
+  };
+  if (LATE) issue_neighbour_traces<C, 1, NEQ>(sFI, TA, 2 * NEQ * C::NF, NEQ, ta1, tid);
+  trace_lines<C, 0, NEQ>(sUp, sJ, ct, tid);
+  block_sync<C::BLOCK>();  // own traces complete (boundary faces copy them)
+  store_neighbour_traces<C, NEQ>(ta0, sJ, sJ + NEQ * C::TN, tid);
+  block_sync<C::BLOCK>();
+  jump(std::integral_constant<int, 0>());
+  if (LATE && DIM == 3) issue_neighbour_traces<C, (DIM == 3 ? 2 : 0), NEQ>(sFI, TA, 2 * NEQ * C::NF, NEQ, ta2, tid);
+  trace_lines<C, 1, NEQ>(sUp, sJ, ct, tid);
+  block_sync<C::BLOCK>();
+  store_neighbour_traces<C, NEQ>(ta1, sJ, sJ + NEQ * C::TN, tid);
+  block_sync<C::BLOCK>();
+  jump(std::integral_constant<int, 1>());
+  if (DIM == 3) {
+    trace_lines<C, (DIM == 3 ? 2 : 0), NEQ>(sUp, sJ, ct, tid);
+    block_sync<C::BLOCK>();
+    store_neighbour_traces<C, NEQ>(ta2, sJ, sJ + NEQ * C::TN, tid);
+    block_sync<C::BLOCK>();
+    jump(std::integral_constant<int, (DIM == 3 ? 2 : 0)>());
   }
   // non-collocated: gradUp = Me^-1 (Ke Up + face terms), dense (src/gradients.cpp:198-229)
   if constexpr (C::NC) {
@@ -2287,58 +2230,54 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && PH::HEAVY) ? 1 : PH::minw_grad(
   if (L::G_IN_LDS) block_sync<C::BLOCK>();
   STAMP(4);
   if constexpr (L::LEAN3D) {
-    if (!(TPSRHS_ABLATE & 16)) {
-      // the lean face kernel reads the gradient back from the vector written above (same lanes, same addresses), after
-      // the stores have been acknowledged.  The memory clobber keeps the compiler from satisfying those reads from the
-      // registers that held g (which would keep all 36 of them alive across the closure).
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const double *gq = gradUp;
-      const unsigned node = static_cast<unsigned>(e0 + le_n) * C::NPE + nd;
-      if constexpr (PH::LEAN_ONE_HEX && C::EPB == 1 && C::BLOCK % C::LN == 0 && !TPSRHS_ABLATE && !TPSRHS_LEAN_GENERAL)
-        visc_phase_lean1<C, PH>(m, sFI, prm, e0, sU, gq, node_on, sJ, sUp, sW, sV, tab, ct, TB, tid STAMP_ARG);
-      else
-        visc_phase_lean3d<C, PH>(m, sFI, prm, e0, sU, gq, node_on, node, sJ, sUp, sW, sV, tab, ct, TB, tid STAMP_ARG);
-    }
+    // the lean face kernel reads the gradient back from the vector written above (same lanes, same addresses), after
+    // the stores have been acknowledged.  The memory clobber keeps the compiler from satisfying those reads from the
+    // registers that held g (which would keep all 36 of them alive across the closure).
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const double *gq = gradUp;
+    const unsigned node = static_cast<unsigned>(e0 + le_n) * C::NPE + nd;
+    if constexpr (PH::LEAN_ONE_HEX && C::EPB == 1 && C::BLOCK % C::LN == 0 && !TPSRHS_LEAN_GENERAL)
+      visc_phase_lean1<C, PH>(m, sFI, prm, e0, sU, gq, node_on, sJ, sUp, sW, sV, tab, ct, TB, tid STAMP_ARG);
+    else
+      visc_phase_lean3d<C, PH>(m, sFI, prm, e0, sU, gq, node_on, node, sJ, sUp, sW, sV, tab, ct, TB, tid STAMP_ARG);
     STAMP_FLUSH();
     return;
   }
 
   // ---- viscous normal-flux traces (T chunk in the sUp region: the nodal Up values are dead)
-  if (!(TPSRHS_ABLATE & 16)) {
-    if constexpr (DIM == 2) {
-      if constexpr (PH::HEAVY) {
-        // mixing-length model (tpsrhs_set_mixing_length): the nodal wall distance of the block's elements
-        __shared__ double sDist[C::NODES];
-        const bool ml_on = m.ml.distance != nullptr;  // uniform over the grid
-        if (ml_on) {
-          if (tid < C::NODES)
-            sDist[tid] = node_on ? m.ml.distance[static_cast<int64_t>(e0 + le_n) * C::NPE + nd] : 0.0;
-          block_sync<C::BLOCK>();
-        }
-        visc_phase_2d<C, PH>(m, sFI, prm, e0, sU, g, node_on, sJ, sUp, sV, tab, ct, TB, tid, ml_on ? sDist : nullptr);
-      } else {
-        visc_phase_2d<C, PH>(m, sFI, prm, e0, sU, g, node_on, sJ, sUp, sV, tab, ct, TB, tid);
+  if constexpr (DIM == 2) {
+    if constexpr (PH::HEAVY) {
+      // mixing-length model (tpsrhs_set_mixing_length): the nodal wall distance of the block's elements
+      __shared__ double sDist[C::NODES];
+      const bool ml_on = m.ml.distance != nullptr;  // uniform over the grid
+      if (ml_on) {
+        if (tid < C::NODES)
+          sDist[tid] = node_on ? m.ml.distance[static_cast<int64_t>(e0 + le_n) * C::NPE + nd] : 0.0;
+        block_sync<C::BLOCK>();
       }
-    } else if constexpr (PH::TWO_STEP && C::Q_ROUNDS == 1 && !(TPSRHS_ABLATE & 256)) {
-      visc_phase_heavy3d<C, PH>(m, sFI, prm, e0, sU, sJ, sUp, sW, sV, tab, ct, TB, tid STAMP_ARG);
-    } else if constexpr (PH::HEAVY) {
-#pragma clang loop unroll(disable)
-      for (int d = 0; d < DIM; d++) {
-        double v[C::Q_ROUNDS][L::NVF];
-        if (d == 0)
-          visc_interp_dir<C, PH, 0>(sU, g, node_on, sJ, sUp, sW, tab, ct, v, tid);
-        else if (d == 1)
-          visc_interp_dir<C, PH, 1>(sU, g, node_on, sJ, sUp, sW, tab, ct, v, tid);
-        else
-          visc_interp_dir<C, PH, (DIM == 3 ? 2 : 0)>(sU, g, node_on, sJ, sUp, sW, tab, ct, v, tid);
-        visc_points<C, PH>(m, sFI, prm, e0, d, v, sV, tab, TB, tid);
-      }
+      visc_phase_2d<C, PH>(m, sFI, prm, e0, sU, g, node_on, sJ, sUp, sV, tab, ct, TB, tid, ml_on ? sDist : nullptr);
     } else {
-      visc_traces_dir<C, PH, 0>(m, sFI, prm, e0, sU, g, node_on, sJ, sUp, sW, sV, tab, ct, TB, tid);
-      visc_traces_dir<C, PH, 1>(m, sFI, prm, e0, sU, g, node_on, sJ, sUp, sW, sV, tab, ct, TB, tid);
-      if (DIM == 3)
-        visc_traces_dir<C, PH, (DIM == 3 ? 2 : 0)>(m, sFI, prm, e0, sU, g, node_on, sJ, sUp, sW, sV, tab, ct, TB, tid);
+      visc_phase_2d<C, PH>(m, sFI, prm, e0, sU, g, node_on, sJ, sUp, sV, tab, ct, TB, tid);
     }
+  } else if constexpr (PH::TWO_STEP && C::Q_ROUNDS == 1) {
+    visc_phase_heavy3d<C, PH>(m, sFI, prm, e0, sU, sJ, sUp, sW, sV, tab, ct, TB, tid STAMP_ARG);
+  } else if constexpr (PH::HEAVY) {
+#pragma clang loop unroll(disable)
+    for (int d = 0; d < DIM; d++) {
+      double v[C::Q_ROUNDS][L::NVF];
+      if (d == 0)
+        visc_interp_dir<C, PH, 0>(sU, g, node_on, sJ, sUp, sW, tab, ct, v, tid);
+      else if (d == 1)
+        visc_interp_dir<C, PH, 1>(sU, g, node_on, sJ, sUp, sW, tab, ct, v, tid);
+      else
+        visc_interp_dir<C, PH, (DIM == 3 ? 2 : 0)>(sU, g, node_on, sJ, sUp, sW, tab, ct, v, tid);
+      visc_points<C, PH>(m, sFI, prm, e0, d, v, sV, tab, TB, tid);
+    }
+  } else {
+    visc_traces_dir<C, PH, 0>(m, sFI, prm, e0, sU, g, node_on, sJ, sUp, sW, sV, tab, ct, TB, tid);
+    visc_traces_dir<C, PH, 1>(m, sFI, prm, e0, sU, g, node_on, sJ, sUp, sW, sV, tab, ct, TB, tid);
+    if (DIM == 3)
+      visc_traces_dir<C, PH, (DIM == 3 ? 2 : 0)>(m, sFI, prm, e0, sU, g, node_on, sJ, sUp, sW, sV, tab, ct, TB, tid);
   }
   STAMP_FLUSH();
 }
@@ -2759,10 +2698,7 @@ __device__ inline void face_flux_dir(const MeshDev &m, typename PH::PRef prm, in
     PH::clamp_species(u1);
     double n[DIM], wq, Xq[DIM];
     face_geometry<C, D>(&sV[le * C::NV * DIM], tab, s, q, n, wq, Xq);
-    if (TPSRHS_ABLATE & 4) {
-#pragma unroll
-      for (int eq = 0; eq < NEQ; eq++) fh[rd][eq] = u1[eq] + u2[eq] * n[0];
-    } else if (nb >= 0) {
+    if (nb >= 0) {
       PH::clamp_species(u2);
       PH::riemann(prm, u1, u2, n, fh[rd]);
 #pragma unroll
@@ -2822,7 +2758,7 @@ __device__ inline void issue_visc_traces_2d(const int2 *sFI, int e0, const doubl
       const int lslot = (pf >> 1) * C::NFACES + 2 * d + (pf & 1);
       const int2 fi = sFI[lslot];
       t.nb[r] = fi.x;
-      if (fi.x != INT32_MIN && !(TPSRHS_ABLATE & 1)) {
+      if (fi.x != INT32_MIN) {
         const double *o = TB + (static_cast<int64_t>(e0) * C::NFACES + lslot) * ((NEQ - 1) * C::NQ) + q;
 #pragma unroll
         for (int k = 1; k < NEQ; k++) t.own[r][k] = o[(k - 1) * C::NQ];
@@ -2937,7 +2873,7 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && (PH::HEAVY || PH::MINW_FLUX > 2
   const int tid = threadIdx.x;
   const int lin = xcd_block(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x), m.reverse);
   const int bid = m.blocks ? m.blocks[lin] : lin;
-  const int e0 = (TPSRHS_ABLATE & 512) ? (bid % 8) * C::EPB : bid * C::EPB;  // (512: timing experiment, as in k_gradient)
+  const int e0 = bid * C::EPB;
   __shared__ int2 sFI[C::EPB * C::NFACES];
   FSTAMP_DECL;
   const bool node_on = tid < C::NODES && (e0 + tid / C::NPE) < m.ne;
@@ -2963,19 +2899,14 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && (PH::HEAVY || PH::MINW_FLUX > 2
   // the neighbour records of the first direction pair go out before the nodal physics (their latency hides behind it)
   // -- except in the wide 2-D kernels (more than 8 equations): 3 x NEQ values held across the closure there are 66
   // VGPRs of a kernel that otherwise spills 90 (torch6, round 2); those issue them where the face term starts
-  constexpr bool EARLY = !(DIM == 2 && NEQ > 8) && !TPSRHS_FLUX_LATE;
+  constexpr bool EARLY = !(DIM == 2 && NEQ > 8);
   if (EARLY) {
     issue_neighbour_traces<C, 0, NEQ>(sFI, TA, 2 * NEQ * C::NF, 0, ta0, tid);
     if (!L::BOTH_2D) issue_visc_traces<C, 0, NEQ>(sFI, e0, TB, tb0, tid);
   }
-  constexpr bool PARK = TPSRHS_FLUX_PARK_GRAD && PH::TWO_STEP && !C::NC && DIM == 3;
   if (node_on) {
 #pragma unroll
     for (int eq = 0; eq < NEQ; eq++) sU[eq * C::NODES + tid] = u[eq];
-    if constexpr (PARK) {  // (the lane's own column of sGf: overwritten by the lane's own flux at the end of the nodal physics)
-#pragma unroll
-      for (int k = 0; k < NEQ * DIM; k++) sGf[k * C::NODES + tid] = gr[k];
-    }
   }
   block_sync<C::BLOCK>();  // tables + vertices + sU
   FSTAMP(1);
@@ -3009,13 +2940,6 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && (PH::HEAVY || PH::MINW_FLUX > 2
       speed = PH::max_char_speed(prm, uc, st);
       typename PH::FluxCoef fc;
       if constexpr (PH::TWO_STEP) PH::flux_coeffs(prm, uc, st, fc);
-      if constexpr (PARK) {  // back from the LDS, through a pointer the compiler cannot see through (no store-to-load forwarding,
-                             // which would keep the 2 * NEQ * DIM registers alive across the closure)
-        const double *pg = sGf + tid;
-        asm volatile("" : "+v"(pg) : : "memory");
-#pragma unroll
-        for (int k = 0; k < NEQ * DIM; k++) gr[k] = pg[k * C::NODES];
-      }
       if (PH::HAS_SOURCE) {
         double up[NEQ];
         PH::prim(prm, u, up);
@@ -3023,33 +2947,28 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && (PH::HEAVY || PH::MINW_FLUX > 2
         if constexpr (PH::AXISYM) PH::axisym_source(prm, u, up, gr, radius, src);
       }
 
-      if (TPSRHS_ABLATE & 2) {
+      if constexpr (PH::HEAVY && DIM == 2) {  // (+ the mixing-length eddy viscosity when a distance function is set)
+        const bool ml_on = m.ml.distance != nullptr;
+        __shared__ double sVsw[C::BLOCK];
+        const EddyCtx ec = closure_ctx(m, true, ml_on ? m.ml.distance[static_cast<int64_t>(e0 + le_n) * C::NPE + nd] : 0.0, Xn, sVsw);
+        if constexpr (PH::TWO_STEP)
+          PH::total_flux(prm, uc, st, fc, gr, PH::AXISYM ? radius : -1.0, F, ec);
+        else
+          PH::total_flux(prm, uc, st, gr, radius, F, ec);
+      } else if constexpr (PH::TWO_STEP)
+        PH::total_flux(prm, uc, st, fc, gr, PH::AXISYM ? radius : -1.0, F);
+      else if constexpr (PH::AXISYM)
+        PH::total_flux(prm, uc, st, gr, radius, F);
+      else if constexpr (PH::LES) {  // elSize and xyz of the node, src/rhs_operator.cpp:526-539
+        PointCtx pc;
+        double xn[DIM];
 #pragma unroll
-        for (int k = 0; k < NEQ * DIM; k++) F[k] = uc[k % NEQ] + gr[k];
-      } else {
-        if constexpr (PH::HEAVY && DIM == 2) {  // (+ the mixing-length eddy viscosity when a distance function is set)
-          const bool ml_on = m.ml.distance != nullptr;
-          __shared__ double sVsw[C::BLOCK];
-          const EddyCtx ec = closure_ctx(m, true, ml_on ? m.ml.distance[static_cast<int64_t>(e0 + le_n) * C::NPE + nd] : 0.0, Xn, sVsw);
-          if constexpr (PH::TWO_STEP)
-            PH::total_flux(prm, uc, st, fc, gr, PH::AXISYM ? radius : -1.0, F, ec);
-          else
-            PH::total_flux(prm, uc, st, gr, radius, F, ec);
-        } else if constexpr (PH::TWO_STEP)
-          PH::total_flux(prm, uc, st, fc, gr, PH::AXISYM ? radius : -1.0, F);
-        else if constexpr (PH::AXISYM)
-          PH::total_flux(prm, uc, st, gr, radius, F);
-        else if constexpr (PH::LES) {  // elSize and xyz of the node, src/rhs_operator.cpp:526-539
-          PointCtx pc;
-          double xn[DIM];
-#pragma unroll
-          for (int d = 0; d < DIM; d++) xn[d] = tab.x[idx[d]];
-          position<DIM>(&sV[le_n * C::NV * DIM], xn, pc.X);
-          pc.delta = prm.elem_delta[e0 + le_n];
-          PH::total_flux(prm, uc, st, gr, F, &pc);
-        } else
-          PH::total_flux(prm, uc, st, gr, F);
-      }
+        for (int d = 0; d < DIM; d++) xn[d] = tab.x[idx[d]];
+        position<DIM>(&sV[le_n * C::NV * DIM], xn, pc.X);
+        pc.delta = prm.elem_delta[e0 + le_n];
+        PH::total_flux(prm, uc, st, gr, F, &pc);
+      } else
+        PH::total_flux(prm, uc, st, gr, F);
     }
     __builtin_amdgcn_sched_barrier(0);
     double xi[DIM], J[DIM * DIM], A[DIM * DIM];
@@ -3136,9 +3055,8 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && (PH::HEAVY || PH::MINW_FLUX > 2
       double acc = 0.0;
 #pragma unroll
       for (int mm = 0; mm < DIM; mm++) {
-        const int m2 = ((TPSRHS_ABLATE & 128) && DIM == 3) ? 2 : mm;  // timing experiment
-        const int sd = stride_of<C>(m2);
-        const double *F = &sGf[(eq + mm * NEQ) * C::NODES + le_n * C::NPE + nd - idx[m2] * sd];
+        const int sd = stride_of<C>(mm);
+        const double *F = &sGf[(eq + mm * NEQ) * C::NODES + le_n * C::NPE + nd - idx[mm] * sd];
 #pragma unroll
         for (int a = 0; a < C::N1; a++) acc += Dc[mm][a] * ldsr(&F[a * sd]);
       }
@@ -3150,14 +3068,12 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && (PH::HEAVY || PH::MINW_FLUX > 2
 
   // ---- face term
   if constexpr (L::BOTH_2D) {
-    if (!(TPSRHS_ABLATE & 8)) {
-      NbTraces<C, NEQ> ta1;
-      NbFlux2<C, NEQ> tb;
-      issue_neighbour_traces<C, 1, NEQ>(sFI, TA, 2 * NEQ * C::NF, 0, ta1, tid);
-      issue_visc_traces_2d<C, NEQ>(sFI, e0, TB, tb, tid);
-      face_flux_2d<C, PH>(m, prm, e0, sU, sX, sY, sV, tab, ct, ta0, ta1, tb, node_on, le_n, idx, z, tid);
-    }
-  } else if (!(TPSRHS_ABLATE & 8)) {  // one direction pair at a time
+    NbTraces<C, NEQ> ta1;
+    NbFlux2<C, NEQ> tb;
+    issue_neighbour_traces<C, 1, NEQ>(sFI, TA, 2 * NEQ * C::NF, 0, ta1, tid);
+    issue_visc_traces_2d<C, NEQ>(sFI, e0, TB, tb, tid);
+    face_flux_2d<C, PH>(m, prm, e0, sU, sX, sY, sV, tab, ct, ta0, ta1, tb, node_on, le_n, idx, z, tid);
+  } else {  // one direction pair at a time
     // software pipeline over the direction pairs: the traces of pair d+1 are in flight while pair d runs
     NbTraces<C, NEQ> ta1, ta2;
     NbFlux<C, NEQ> tb1, tb2;
