@@ -431,6 +431,34 @@ int tpsrhs_rk4_step(tpsrhs_handle h, double *x, double *time, double dt, double 
 int tpsrhs_advance(tpsrhs_handle h, double *x, double *time, double *dt, int num_steps, int constant_dt, double cfl,
                    double hmin, int64_t *nan_count);
 
+/* The reference's other explicit integrators: `time/integrator` selects one of five (src/M2ulPhyS.cpp:2722-2736) and
+ * the constructor builds MFEM's ForwardEulerSolver, RK2Solver(1.0), RK3SSPSolver, RK4Solver or RK6Solver from it
+ * (src/M2ulPhyS.cpp:721-739) [third party: MFEM >= 4.4, linalg/ode.cpp].  The values are the reference's
+ * timeIntegratorType.  In MFEM's order of operations, with k = f(.) one Mult:
+ *   forward Euler   k = f(x);  x = x + dt*k
+ *   RK2(a = 1)      k = f(x);  x1 = x + (dt/2)*k;  y = x + dt*k;  k = f(y);  x = x1 + (dt/2)*k
+ *   RK3-SSP         k = f(x);  y = x + dt*k
+ *                   k = f(y);  y = y + dt*k;  y = (3/4)*x + (1/4)*y
+ *                   k = f(y);  y = y + dt*k;  x = (1/3)*x + (2/3)*y
+ * Forward Euler, RK2 and RK3-SSP run the plain Mult followed by one streaming kernel per stage (each stage one pass
+ * over the state: 3 / 7 / 11 state vectors of traffic per step); TPSRHS_RK4 is tpsrhs_rk4_step / tpsrhs_advance
+ * themselves, bit for bit.  TPSRHS_RK6 (MFEM's eight-stage Verner scheme, which no input of the reference selects)
+ * returns TPSRHS_ERR_UNSUPPORTED, any other value TPSRHS_ERR_INVALID_ARGUMENT, both before any device work. */
+enum tpsrhs_integrator { TPSRHS_FORWARD_EULER = 1, TPSRHS_RK2 = 2, TPSRHS_RK3_SSP = 3, TPSRHS_RK4 = 4, TPSRHS_RK6 = 6 };
+
+/* tpsrhs_rk4_step for any built integrator, argument for argument: x updated in place, *time += dt, max_char_speed
+ * the value left by the LAST Mult of the step, Check_NAN and then (USER_DEFINED fluids) Check_Undershoot applied
+ * once, to the final state of the step (src/M2ulPhyS.cpp:2004-2008).  The non-reflecting boundary state advances by
+ * dt in every Mult, as in the reference: once per Euler step, twice per RK2 step, three times per RK3 step. */
+int tpsrhs_step(tpsrhs_handle h, int integrator, double *x, double *time, double dt, double *max_char_speed,
+                int64_t *nan_count);
+
+/* tpsrhs_advance for any built integrator, argument for argument (the variable step, its MIN reduce hook, the
+ * captured step graph, the read-back at the end are shared; a graph captured for one scheme is never replayed for
+ * another). */
+int tpsrhs_advance_with(tpsrhs_handle h, int integrator, double *x, double *time, double *dt, int num_steps,
+                        int constant_dt, double cfl, double hmin, int64_t *nan_count);
+
 /* The time step the non-reflecting boundary conditions integrate their boundary state with: the reference's
  * BoundaryCondition holds a reference to M2ulPhyS::dt (src/BoundaryCondition.hpp:54) and advances `boundaryU`
  * by dt in EVERY Mult (src/outletBC.cpp:712-724).  tpsrhs_rk4_step sets it itself. */

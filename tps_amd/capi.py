@@ -33,6 +33,21 @@ SUB_P, SUB_P_NR, SUB_MF_NR, SUB_MF_NR_PW = 0, 2, 3, 4
 INV, SLIP, VISC_ADIAB, VISC_ISOTH, VISC_GNRL = 0, 1, 2, 3, 4
 ADIAB, ISOTH, SHTH, NONE_THMCND = 0, 1, 2, 3  # ThermalCondition of viscous_general walls
 
+# tpsrhs_integrator: the reference's timeIntegratorType (src/M2ulPhyS.cpp:2722-2727) and its `time/integrator` strings
+FORWARD_EULER, RK2, RK3_SSP, RK4, RK6 = 1, 2, 3, 4, 6
+INTEGRATORS = {"forwardEuler": FORWARD_EULER, "rk2": RK2, "rk3": RK3_SSP, "rk4": RK4, "rk6": RK6}
+ERR_INVALID_ARGUMENT, ERR_UNSUPPORTED = 1, 2
+
+
+def integrator_value(integrator):
+    """the enum value of an integrator given as that value or as the reference's input string"""
+    if isinstance(integrator, str):
+        if integrator not in INTEGRATORS:
+            raise ValueError(f"unknown time integrator {integrator!r}: one of {sorted(INTEGRATORS)}")
+        return INTEGRATORS[integrator]
+    return int(integrator)
+
+
 STATUS = {0: "OK", 1: "INVALID_ARGUMENT", 2: "UNSUPPORTED", 3: "MESH", 4: "DEVICE", 5: "NO_DEVICE", 6: "HALO"}
 
 _dp = C.POINTER(C.c_double)
@@ -628,6 +643,9 @@ def load():
     lib.tpsrhs_rk4_step.argtypes = [vp, C.c_void_p, _dp, C.c_double, _dp, C.POINTER(C.c_int64)]
     lib.tpsrhs_advance.argtypes = [vp, C.c_void_p, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double,
                                    C.POINTER(C.c_int64)]
+    lib.tpsrhs_step.argtypes = [vp, C.c_int, C.c_void_p, _dp, C.c_double, _dp, C.POINTER(C.c_int64)]
+    lib.tpsrhs_advance_with.argtypes = [vp, C.c_int, C.c_void_p, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double,
+                                        C.POINTER(C.c_int64)]
     lib.tpsrhs_set_dt.argtypes = [vp, C.c_double]
     lib.tpsrhs_set_forcing.argtypes = [vp, C.POINTER(Forcing)]
     lib.tpsrhs_set_joule_heating.argtypes = [vp, C.c_void_p]
@@ -647,7 +665,7 @@ EXPORTED_SYMBOLS = [
     "tpsrhs_get_primitives", "tpsrhs_get_gradients", "tpsrhs_get_plasma_conductivity", "tpsrhs_height", "tpsrhs_num_dofs", "tpsrhs_num_equation",
     "tpsrhs_enable_kernel_timing", "tpsrhs_kernel_times", "tpsrhs_mult_times", "tpsrhs_kernel_bytes",
     "tpsrhs_eval_pointwise", "tpsrhs_table_eval", "tpsrhs_math_eval", "tpsrhs_face_tables",
-    "tpsrhs_rk4_step", "tpsrhs_advance", "tpsrhs_set_dt", "tpsrhs_set_forcing", "tpsrhs_set_joule_heating", "tpsrhs_set_mixing_length", "tpsrhs_status_string",
+    "tpsrhs_rk4_step", "tpsrhs_advance", "tpsrhs_step", "tpsrhs_advance_with", "tpsrhs_set_dt", "tpsrhs_set_forcing", "tpsrhs_set_joule_heating", "tpsrhs_set_mixing_length", "tpsrhs_status_string",
     "tpsrhs_last_error", "tpsrhs_version",
 ]
 

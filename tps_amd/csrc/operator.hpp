@@ -113,14 +113,17 @@ struct tpsrhs_operator {
   const double *nr_dt_dev = nullptr;  // non-NULL while tpsrhs_advance runs: the boundary conditions read dt there
   tpsrhs_reduce_fn reduce = nullptr;
   void *reduce_ctx = nullptr;
-  // one RK4 step of tpsrhs_advance as an executable graph (dt lives in device memory, so the step replays as is)
+  // one step of tpsrhs_advance / tpsrhs_advance_with as an executable graph (dt lives in device memory, so the step
+  // replays as is); the key holds the integrator: a step captured for one scheme is never replayed for another
   hipGraphExec_t step_graph = nullptr;
   struct StepKey {
     const void *x = nullptr;
     int constant_dt = 0, bstate_cur = 0, epoch = 0;
+    int integrator = TPSRHS_RK4;
     double coef = 0.0;
     bool operator==(const StepKey &o) const {
-      return x == o.x && constant_dt == o.constant_dt && bstate_cur == o.bstate_cur && epoch == o.epoch && coef == o.coef;
+      return x == o.x && constant_dt == o.constant_dt && bstate_cur == o.bstate_cur && epoch == o.epoch &&
+             integrator == o.integrator && coef == o.coef;
     }
   } step_key;
   int config_epoch = 0;  // bumped by everything that changes what a step launches (forcing terms, ...)

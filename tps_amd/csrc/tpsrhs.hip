@@ -8,6 +8,7 @@
 #include "physics_dryair_axisym.hpp"
 #include "physics_plasma.hpp"
 #include "plasma_params_host.hpp"
+#include "time_integrators.hpp"
 
 #include <dlfcn.h>
 
@@ -762,15 +763,70 @@ void rk4_stages(tpsrhs_operator *h, double *x, double dt, const double *dt_dev) 
     in = y;
   }
 }
+
+// Forward Euler, RK2(a = 1) and RK3-SSP: at the end of this file
+void rk_stages(tpsrhs_operator *h, int integrator, double *x, double dt, const double *dt_dev);
+
+// TPSRHS_OK for the integrators that are built; the status of the others, before any device work
+int check_integrator(int integrator, const char *who) {
+  switch (integrator) {
+    case TPSRHS_FORWARD_EULER:
+    case TPSRHS_RK2:
+    case TPSRHS_RK3_SSP:
+    case TPSRHS_RK4: return TPSRHS_OK;
+    case TPSRHS_RK6:
+      return fail(TPSRHS_ERR_UNSUPPORTED, std::string(who) + ": the RK6 integrator (MFEM's eight-stage Verner scheme) is not built; "
+                                              "forwardEuler, rk2, rk3 and rk4 are");
+    default:
+      return fail(TPSRHS_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown integrator " + std::to_string(integrator) +
+                                                   " (the reference's timeIntegratorType: 1, 2, 3, 4 or 6)");
+  }
+}
+
+void step_stages(tpsrhs_operator *h, int integrator, double *x, double dt, const double *dt_dev) {
+  if (integrator == TPSRHS_RK4)
+    rk4_stages(h, x, dt, dt_dev);
+  else
+    rk_stages(h, integrator, x, dt, dt_dev);
+}
+
+int step_with(tpsrhs_handle h, int integrator, const char *who, double *x, double *time, double dt, double *max_char_speed,
+              int64_t *nan_count);
+int advance_with(tpsrhs_handle h, int integrator, const char *who, double *x, double *time, double *dt, int num_steps,
+                 int constant_dt, double cfl, double hmin, int64_t *nan_count);
 }  // namespace
 
 int tpsrhs_rk4_step(tpsrhs_handle h, double *x, double *time, double dt, double *max_char_speed, int64_t *nan_count) {
-  if (!h || !x || !time) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_rk4_step: NULL argument");
+  return step_with(h, TPSRHS_RK4, "tpsrhs_rk4_step", x, time, dt, max_char_speed, nan_count);
+}
+
+int tpsrhs_step(tpsrhs_handle h, int integrator, double *x, double *time, double dt, double *max_char_speed,
+                int64_t *nan_count) {
+  return step_with(h, integrator, "tpsrhs_step", x, time, dt, max_char_speed, nan_count);
+}
+
+int tpsrhs_advance(tpsrhs_handle h, double *x, double *time, double *dt, int num_steps, int constant_dt, double cfl,
+                   double hmin, int64_t *nan_count) {
+  return advance_with(h, TPSRHS_RK4, "tpsrhs_advance", x, time, dt, num_steps, constant_dt, cfl, hmin, nan_count);
+}
+
+int tpsrhs_advance_with(tpsrhs_handle h, int integrator, double *x, double *time, double *dt, int num_steps,
+                        int constant_dt, double cfl, double hmin, int64_t *nan_count) {
+  return advance_with(h, integrator, "tpsrhs_advance_with", x, time, dt, num_steps, constant_dt, cfl, hmin, nan_count);
+}
+
+}  // extern "C"
+
+namespace {
+int step_with(tpsrhs_handle h, int integrator, const char *who, double *x, double *time, double dt, double *max_char_speed,
+              int64_t *nan_count) {
+  if (!h || !x || !time) return fail(TPSRHS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
+  if (const int st = check_integrator(integrator, who)) return st;
   return guarded([&] {
     HIP_CHECK(hipSetDevice(h->device));
     h->nr_dt = dt;  // the boundary conditions see M2ulPhyS::dt (src/BoundaryCondition.hpp:54)
     if (h->d_nan) HIP_CHECK(hipMemsetAsync(h->d_nan, 0, sizeof(unsigned long long), h->stream));
-    rk4_stages(h, x, dt, nullptr);
+    step_stages(h, integrator, x, dt, nullptr);
     *time += dt;
     if (max_char_speed || nan_count) {
       hipLaunchKernelGGL(k_reduce_max<1024>, dim3(1), dim3(1024), 0, h->stream, h->flux_grid, h->d_block_speed, h->d_speed);
@@ -786,11 +842,14 @@ int tpsrhs_rk4_step(tpsrhs_handle h, double *x, double *time, double dt, double 
   });
 }
 
-int tpsrhs_advance(tpsrhs_handle h, double *x, double *time, double *dt, int num_steps, int constant_dt, double cfl,
-                   double hmin, int64_t *nan_count) {
-  if (!h || !x || !time || !dt) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_advance: NULL argument");
+// The stage sequence (step_stages) is all that depends on the integrator: the end of the step, the MIN reduce, the graph,
+// the error paths and the read-back are shared.
+int advance_with(tpsrhs_handle h, int integrator, const char *who, double *x, double *time, double *dt, int num_steps,
+                 int constant_dt, double cfl, double hmin, int64_t *nan_count) {
+  if (!h || !x || !time || !dt) return fail(TPSRHS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
+  if (const int st = check_integrator(integrator, who)) return st;
   if (num_steps < 0 || !(*dt > 0.0) || (!constant_dt && !(cfl > 0.0 && hmin > 0.0)))
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_advance: needs num_steps >= 0, dt > 0 and (constant dt or cfl, hmin > 0)");
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, std::string(who) + ": needs num_steps >= 0, dt > 0 and (constant dt or cfl, hmin > 0)");
   return guarded([&] {
     HIP_CHECK(hipSetDevice(h->device));
     if (!constant_dt && h->topo.num_shared > 0 && !h->reduce)
@@ -802,7 +861,7 @@ int tpsrhs_advance(tpsrhs_handle h, double *x, double *time, double *dt, int num
     if (h->d_nan) HIP_CHECK(hipMemsetAsync(h->d_nan, 0, sizeof(unsigned long long), h->stream));
     h->nr_dt_dev = h->d_ctl;
     auto one_step = [&] {
-      rk4_stages(h, x, 0.0, h->d_ctl);
+      step_stages(h, integrator, x, 0.0, h->d_ctl);
       hipLaunchKernelGGL(k_step_end<1024>, dim3(1), dim3(1024), 0, h->stream, h->flux_grid, h->d_block_speed, h->d_ctl,
                          constant_dt ? 1 : 0, cfl * hmin / static_cast<double>(h->dim));
       HIP_CHECK(hipGetLastError());
@@ -811,15 +870,20 @@ int tpsrhs_advance(tpsrhs_handle h, double *x, double *time, double *dt, int num
           throw std::runtime_error("halo: reduce callback failed");
       }
     };
-    // On one rank a step is a fixed sequence of ~17 launches whose arguments do not change from step to step (dt
+    // On one rank a step is a fixed sequence of launches (~17 for RK4) whose arguments do not change from step to step (dt
     // and the time are in device memory; the two boundary-state buffers swap four times per step): captured once
     // into a hipGraph and replayed -- the launch overhead matters on small meshes.  Needs a capturable stream (not
     // the NULL stream), no host callbacks in the step (partitioned meshes keep the plain loop), no timing events.
     const char *genv = std::getenv("TPSRHS_GRAPH");
     const bool use_graph = h->stream != nullptr && h->topo.num_shared == 0 && !h->timing && num_steps >= 3 &&
                            !(genv && genv[0] == '0');
+    // A replayed graph must leave the boundary-state buffers as it found them, and they swap once per Mult: with
+    // non-reflecting faces a scheme with an odd number of Mults per step (Euler 1, RK3 3) is captured two steps at a time.
+    const int mults_per_step = integrator == TPSRHS_RK4 ? 4 : integrator;
+    const int steps_per_graph = (h->n_nr_faces > 0 && (mults_per_step & 1)) ? 2 : 1;
     h->ta_valid = false;
-    h->ta_chain = !h->forcing_active;  // (with forcing terms the stage kernel runs and nothing is fused)
+    // (with forcing terms the stage kernel runs and nothing is fused; the other integrators never enter the trace chain)
+    h->ta_chain = integrator == TPSRHS_RK4 && !h->forcing_active;
     try {
       int step = 0;
       if (use_graph) {
@@ -830,6 +894,7 @@ int tpsrhs_advance(tpsrhs_handle h, double *x, double *time, double *dt, int num
         key.constant_dt = constant_dt ? 1 : 0;
         key.bstate_cur = h->bstate_cur;
         key.epoch = h->config_epoch;
+        key.integrator = integrator;
         key.coef = cfl * hmin / static_cast<double>(h->dim);
         if (!h->step_graph || !(h->step_key == key)) {
           if (h->step_graph) {
@@ -839,7 +904,7 @@ int tpsrhs_advance(tpsrhs_handle h, double *x, double *time, double *dt, int num
           hipGraph_t g = nullptr;
           HIP_CHECK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
           try {
-            one_step();
+            for (int i = 0; i < steps_per_graph; i++) one_step();
           } catch (...) {
             (void)hipStreamEndCapture(h->stream, &g);
             if (g) (void)hipGraphDestroy(g);
@@ -851,7 +916,7 @@ int tpsrhs_advance(tpsrhs_handle h, double *x, double *time, double *dt, int num
           HIP_CHECK(ie);
           h->step_key = key;
         }
-        for (; step < num_steps; step++) HIP_CHECK(hipGraphLaunch(h->step_graph, h->stream));
+        for (; step + steps_per_graph <= num_steps; step += steps_per_graph) HIP_CHECK(hipGraphLaunch(h->step_graph, h->stream));
       }
       for (; step < num_steps; step++) one_step();
     } catch (...) {
@@ -872,6 +937,9 @@ int tpsrhs_advance(tpsrhs_handle h, double *x, double *time, double *dt, int num
     if (nan_count) *nan_count = static_cast<int64_t>(bad);
   });
 }
+}  // namespace
+
+extern "C" {
 
 int tpsrhs_set_dt(tpsrhs_handle h, double dt) {
   if (!h) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_set_dt: NULL handle");
@@ -1261,3 +1329,56 @@ int tpsrhs_get_plasma_conductivity(tpsrhs_handle h, const double *x, double *sig
 const char *tpsrhs_version(void) { return "tpsrhs 0.1.0 (gfx950)"; }
 
 }  // extern "C"
+
+namespace {
+// Forward Euler, RK2(a = 1) and RK3-SSP (time_integrators.hpp): the plain Mult (h->rk stays RkDev{}: k_flux writes the
+// residual, nothing enters the trace chain) and one k_rk_stage pass per stage.  k | y in the first two thirds of d_rk, y on
+// an even offset so that an odd length keeps the 16-byte accesses.  (Fusing these combinations into k_flux's epilogue, as
+// RK4 has, is left out on purpose: DESIGN.md section 9.)  Defined after every other launch of this unit, so that the
+// compiler numbers the kernels that were here before as it did before (tools/device_asm_diff.py compares their labels too).
+template <int OP>
+void rk_stage(tpsrhs_operator *h, int64_t n, int64_t clamp_lo, int64_t clamp_hi, double dt, const double *dt_dev, double *x,
+              const double *k, double *y) {
+  const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
+  const int64_t items = vec ? (n + 1) / 2 : n;
+  const int grid = static_cast<int>(std::min<int64_t>((items + 255) / 256, 8192));  // the grid cap of k_rk4_stage
+  if (vec)
+    hipLaunchKernelGGL((k_rk_stage<OP, true, 256>), dim3(grid), dim3(256), 0, h->stream, n, clamp_lo, clamp_hi, dt, dt_dev, x, k, y,
+                       h->d_nan);
+  else
+    hipLaunchKernelGGL((k_rk_stage<OP, false, 256>), dim3(grid), dim3(256), 0, h->stream, n, clamp_lo, clamp_hi, dt, dt_dev, x, k, y,
+                       h->d_nan);
+  HIP_CHECK(hipGetLastError());
+}
+
+void rk_stages(tpsrhs_operator *h, int integrator, double *x, double dt, const double *dt_dev) {
+  const int64_t n = static_cast<int64_t>(h->neq) * h->ndofs;
+  if (!h->d_rk) {
+    h->d_rk = dev_alloc<double>(3 * n);
+    h->d_nan = dev_alloc<unsigned long long>(1);
+    HIP_CHECK(hipMemsetAsync(h->d_nan, 0, sizeof(unsigned long long), h->stream));
+  }
+  double *k = h->d_rk, *y = k + ((n + 1) & ~static_cast<int64_t>(1));  // y ends at or before 2 n + 1 <= 3 n
+  h->ta_valid = false;  // every Mult of these schemes runs its own k_traces sweep
+  const bool mixture = h->phys.working_fluid == TPSRHS_USER_DEFINED;
+  const int sp_first = h->nvel + 2;
+  const int sp_last = mixture ? sp_first + (h->phys.mixture.ambipolar ? h->phys.mixture.num_species - 2
+                                                                       : h->phys.mixture.num_species - 1)
+                              : sp_first;
+  const int64_t lo = sp_first * h->ndofs, hi = sp_last * h->ndofs;  // Check_Undershoot's rows, contiguous in [neq][ndofs]
+  h->launch(h, x, k, false);  // k = f(x); SetTime is a no-op for this operator
+  if (integrator == TPSRHS_FORWARD_EULER) {
+    rk_stage<RK_EULER>(h, n, lo, hi, dt, dt_dev, x, k, y);
+  } else if (integrator == TPSRHS_RK2) {
+    rk_stage<RK2_STAGE1>(h, n, lo, hi, dt, dt_dev, x, k, y);
+    h->launch(h, y, k, false);
+    rk_stage<RK2_STAGE2>(h, n, lo, hi, dt, dt_dev, x, k, y);
+  } else {
+    rk_stage<RK3_STAGE1>(h, n, lo, hi, dt, dt_dev, x, k, y);
+    h->launch(h, y, k, false);
+    rk_stage<RK3_STAGE2>(h, n, lo, hi, dt, dt_dev, x, k, y);
+    h->launch(h, y, k, false);
+    rk_stage<RK3_STAGE3>(h, n, lo, hi, dt, dt_dev, x, k, y);
+  }
+}
+}  // namespace

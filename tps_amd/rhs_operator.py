@@ -158,15 +158,43 @@ class RHSoperator:
             self.nan_count = bad.value
         return t.value
 
-    def advance(self, x: torch.Tensor, time: float, dt: float, num_steps: int, constant_dt=True, cfl=0.0, hmin=0.0):
+    def step(self, x: torch.Tensor, time: float, dt: float, integrator, want_max_char_speed=False, want_nan_count=False):
+        """``rk4_step`` for any of the reference's integrators that are built (``time/integrator``,
+        ``src/M2ulPhyS.cpp:721-739, 2722-2736``): ``integrator`` is the enum value (``capi.FORWARD_EULER`` ...) or the
+        input string ``forwardEuler``, ``rk2``, ``rk3``, ``rk4``; ``rk6`` raises (UNSUPPORTED)."""
+        self._check(x)
+        t = C.c_double(time)
+        speed = C.c_double(0.0)
+        bad = C.c_int64(0)
+        st = self._lib.tpsrhs_step(self._h, capi.integrator_value(integrator), C.c_void_p(x.data_ptr()), C.byref(t), float(dt),
+                                   C.byref(speed) if want_max_char_speed else None,
+                                   C.byref(bad) if want_nan_count else None)
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_step")
+        if want_max_char_speed:
+            self.max_char_speed = speed.value
+        if want_nan_count:
+            self.nan_count = bad.value
+        return t.value
+
+    def advance(self, x: torch.Tensor, time: float, dt: float, num_steps: int, constant_dt=True, cfl=0.0, hmin=0.0,
+                integrator="rk4"):
         """``num_steps`` times ``M2ulPhyS::solveStep`` (``src/M2ulPhyS.cpp:2004-2019``) with dt, time and the NaN
-        census on the device; returns ``(time, next dt, NaN count)`` after ONE synchronisation at the end."""
+        census on the device; returns ``(time, next dt, NaN count)`` after ONE synchronisation at the end.
+        ``integrator``: as in :meth:`step`; the default is ``tpsrhs_advance`` itself."""
         self._check(x)
         t, d, bad = C.c_double(time), C.c_double(dt), C.c_int64(0)
-        st = self._lib.tpsrhs_advance(self._h, C.c_void_p(x.data_ptr()), C.byref(t), C.byref(d), int(num_steps),
-                                      1 if constant_dt else 0, float(cfl), float(hmin), C.byref(bad))
-        if st != 0:
-            raise TpsRhsError(st, "tpsrhs_advance")
+        which = capi.integrator_value(integrator)
+        if which == capi.RK4:
+            st = self._lib.tpsrhs_advance(self._h, C.c_void_p(x.data_ptr()), C.byref(t), C.byref(d), int(num_steps),
+                                          1 if constant_dt else 0, float(cfl), float(hmin), C.byref(bad))
+            if st != 0:
+                raise TpsRhsError(st, "tpsrhs_advance")
+        else:
+            st = self._lib.tpsrhs_advance_with(self._h, which, C.c_void_p(x.data_ptr()), C.byref(t), C.byref(d), int(num_steps),
+                                               1 if constant_dt else 0, float(cfl), float(hmin), C.byref(bad))
+            if st != 0:
+                raise TpsRhsError(st, "tpsrhs_advance_with")
         return t.value, d.value, bad.value
 
     def setDt(self, dt: float):
