@@ -459,6 +459,50 @@ int tpsrhs_step(tpsrhs_handle h, int integrator, double *x, double *time, double
 int tpsrhs_advance_with(tpsrhs_handle h, int integrator, double *x, double *time, double *dt, int num_steps,
                         int constant_dt, double cfl, double hmin, int64_t *nan_count);
 
+/* ---- running statistics sampled in the time loop -------------------------------------------------------------------
+ * What the reference's time loop does once per iteration besides solveStep: `average->addSample(iter, d_mixture)`
+ * (src/M2ulPhyS.cpp:2099; src/averaging.cpp:198-234 the sampling condition and the counters, :331-435 the update) -- the
+ * running mean of the primitive state and the running velocity covariances (the "rms" field), which the reference stores
+ * as /meanSolution and /rmsData.
+ *   mean[num_equation][NDofs]  in the layout of x and of tpsrhs_get_primitives (byNODES)
+ *   vari[nvar][NDofs]          nvar = nvel (nvel + 1) / 2: the diagonal first, then the pairs i < j in row-major order --
+ *                              uu vv ww uv uw vw for three velocity components, uu vv uv for two (src/M2ulPhyS.cpp:665-675)
+ *   ns_mean, ns_vari           samples in each (apart, because restartRMS zeroes one and not the other)
+ *   iter                       the step counter of the loop
+ * One sample of a state x: s = prim(x) with the temperature row 1 + nvel replaced by the pressure; for every row
+ * mean = (ns_mean mean + s) / (ns_mean + 1); then, with the UPDATED mean and d_i = s_i - mean_i of the velocity rows,
+ * vari = (vari ns_vari + d_i d_j) / (ns_vari + 1); then both counters go up by one.  A field whose counter is 0 counts
+ * as zero.  This is the reference's recurrence, not the textbook variance: two samples a, b give (b - a)^2 / 8.
+ * Inside tpsrhs_advance / tpsrhs_advance_with, after every step: iter += 1, and if iter % sample_interval == 0 and
+ * iter >= start_iter (the reference's sampleFreq and startIter) one sample of the new x is enqueued between the steps;
+ * nothing returns to the host, the captured step graph is neither part of it nor re-captured because of it.
+ * tpsrhs_step and tpsrhs_rk4_step neither count nor sample: a caller that drives the loop itself calls
+ * tpsrhs_stats_add_sample.  Partitioned meshes need nothing more: the update is local to a node.
+ * Two deliberate differences from the reference:
+ *  (a) it samples the grid function Up, which holds the primitives of the input of the step's LAST Mult (a stage
+ *      state); here the primitives of the new x are sampled, after Check_NAN and Check_Undershoot, whatever the integrator;
+ *  (b) it replaces row 1 + dim by the pressure, which in the axisymmetric formulation (dim 2, three velocity
+ *      components) is the swirl velocity; here it is the temperature row 1 + nvel in every formulation.
+ * Every entry but tpsrhs_stats_configure returns TPSRHS_ERR_INVALID_ARGUMENT, before any device work, on an operator
+ * whose statistics are not configured.  All pointers to fields are DEVICE pointers; the copies are ordered on the
+ * operator's stream and do not synchronise (as tpsrhs_get_primitives). */
+
+/* Allocates the fields (zero) and zeroes the counters and iter; compute_variances = 0: the mean only.  sample_interval
+ * 0 switches statistics off and frees everything; a negative interval or start: TPSRHS_ERR_INVALID_ARGUMENT. */
+int tpsrhs_stats_configure(tpsrhs_handle h, int64_t sample_interval, int64_t start_iter, int compute_variances);
+/* The step counter the loop continues from (`iter` of a restart file). */
+int tpsrhs_stats_set_iter(tpsrhs_handle h, int64_t iter);
+/* One unconditional sample of the device vector x (iter is not touched). */
+int tpsrhs_stats_add_sample(tpsrhs_handle h, const double *x);
+/* Any pointer may be NULL. */
+int tpsrhs_stats_get(tpsrhs_handle h, double *mean_out, double *vari_out, int *ns_mean, int *ns_vari, int64_t *iter);
+/* Continuation (the reference's enableContinuation: samplesMean / samplesRMS and the two fields of a restart file).
+ * vari == NULL or ns_vari == 0 is restartRMS: the covariances start again, the mean goes on.  ns_mean == 0 starts
+ * the mean again too (mean may then be NULL). */
+int tpsrhs_stats_set(tpsrhs_handle h, const double *mean, const double *vari, int ns_mean, int ns_vari);
+/* nvar, or 0 when only the mean is kept */
+int tpsrhs_stats_num_variances(tpsrhs_handle h, int *num_variances);
+
 /* The time step the non-reflecting boundary conditions integrate their boundary state with: the reference's
  * BoundaryCondition holds a reference to M2ulPhyS::dt (src/BoundaryCondition.hpp:54) and advances `boundaryU`
  * by dt in EVERY Mult (src/outletBC.cpp:712-724).  tpsrhs_rk4_step sets it itself. */

@@ -1,6 +1,9 @@
 """Wall-clock time of one step of the device time loop, and of one Mult next to it (run on a GPU box):
     python tools/rk4_time.py [--integrator forwardEuler|rk2|rk3|rk4] [--workload cfg2|argon_p3|...] [--steps N]
-rk4 goes through rk4_step, the others through step (tpsrhs_step); every step returns to the host, as a driver's loop does."""
+rk4 goes through rk4_step, the others through step (tpsrhs_step); every step returns to the host, as a driver's loop does.
+    python tools/rk4_time.py --advance [--stats-interval K] ...
+times the steps inside ONE advance call instead (tpsrhs_advance / tpsrhs_advance_with on a side stream, constant dt, the
+captured step graph), with the running statistics sampled every K steps (0: off), and one add_sample on its own."""
 import argparse
 import os
 import sys
@@ -19,12 +22,17 @@ ap.add_argument("--integrator", default="rk4", choices=sorted(set(capi.INTEGRATO
 ap.add_argument("--workload", default="cfg2", help="cfg2 (BASELINE configs[1]) or a workload of bench.py, e.g. argon_p3")
 ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--dt", type=float, default=None, help="default: 1e-7 (cfg2), 1e-10 (the others: stiff chemistry)")
+ap.add_argument("--advance", action="store_true", help="time the steps of one advance call (the device loop)")
+ap.add_argument("--stats-interval", type=int, default=0, help="--advance: sample the running statistics every K steps")
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
 
+side = torch.cuda.Stream() if args.advance else None  # a capturable stream: advance replays its step graph
+if side is not None:
+    torch.cuda.set_stream(side)
 if args.workload == "cfg2":
     c = cases.config(2)
-    op = RHSoperator(c.mesh, c.disc, c.physics, c.bcs)
+    op = RHSoperator(c.mesh, c.disc, c.physics, c.bcs, stream=side)
     U, dt = c.state(), 1e-7
 else:
     import bench  # noqa: E402
@@ -32,11 +40,39 @@ else:
     order, physics, make_bcs, make_state, _, _ = bench.workload(args.workload)
     mesh = meshgen.ogrid_cylinder_slab(28, 112, 16, 0, 1)
     U, dt = make_state(node_coordinates(mesh, order), physics), 1e-10
-    op = RHSoperator(mesh, capi.Disc(order, 0, 0, 0, 0), physics, make_bcs(physics))
+    op = RHSoperator(mesh, capi.Disc(order, 0, 0, 0, 0), physics, make_bcs(physics), stream=side)
 if args.dt is not None:
     dt = args.dt
 x = torch.tensor(U.ravel(), dtype=torch.float64, device=op.device)
 y = torch.empty_like(x)
+
+
+if args.advance:
+    if args.stats_interval:
+        op.configureStatistics(args.stats_interval)
+    t, _, _ = op.advance(x, 0.0, dt, 4, True, integrator=args.integrator)  # allocations, the capture
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    t, _, bad = op.advance(x, t, dt, args.steps, True, integrator=args.integrator)
+    torch.cuda.synchronize()
+    el = (time.perf_counter() - t0) / args.steps
+    line = (f"{args.workload} {args.integrator} advance, statistics every {args.stats_interval or 'never'}: step ms {el * 1e3:.4f}  "
+            f"NaN {bad}  finite {bool(torch.isfinite(x).all())}")
+    if args.stats_interval:
+        for _ in range(3):
+            op.addSample(x)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            op.addSample(x)
+        torch.cuda.synchronize()
+        one = (time.perf_counter() - t0) / args.steps
+        mean, vari, ns, _, it = op.getStatistics()
+        vectors = 2 * op.num_equation + (op.num_equation + 1) + (op.num_equation + 1) + 2 * op.num_equation + 2 * vari.shape[0]
+        line += (f"  one sample ms {one * 1e3:.4f}  model {vectors} vectors of {op.NDofs * 8 / 1e6:.1f} MB at 5.8 TB/s "
+                 f"{vectors * op.NDofs * 8 / 5.8e12 * 1e3:.4f} ms  samples {ns}  iter {it}  finite {bool(torch.isfinite(mean).all())}")
+    print(line)
+    sys.exit(0)
 
 
 def one_step(t):

@@ -646,6 +646,13 @@ def load():
     lib.tpsrhs_step.argtypes = [vp, C.c_int, C.c_void_p, _dp, C.c_double, _dp, C.POINTER(C.c_int64)]
     lib.tpsrhs_advance_with.argtypes = [vp, C.c_int, C.c_void_p, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double,
                                         C.POINTER(C.c_int64)]
+    _ip32 = C.POINTER(C.c_int)
+    lib.tpsrhs_stats_configure.argtypes = [vp, C.c_int64, C.c_int64, C.c_int]
+    lib.tpsrhs_stats_set_iter.argtypes = [vp, C.c_int64]
+    lib.tpsrhs_stats_add_sample.argtypes = [vp, vp]
+    lib.tpsrhs_stats_get.argtypes = [vp, vp, vp, _ip32, _ip32, C.POINTER(C.c_int64)]
+    lib.tpsrhs_stats_set.argtypes = [vp, vp, vp, C.c_int, C.c_int]
+    lib.tpsrhs_stats_num_variances.argtypes = [vp, _ip32]
     lib.tpsrhs_set_dt.argtypes = [vp, C.c_double]
     lib.tpsrhs_set_forcing.argtypes = [vp, C.POINTER(Forcing)]
     lib.tpsrhs_set_joule_heating.argtypes = [vp, C.c_void_p]
@@ -667,6 +674,8 @@ EXPORTED_SYMBOLS = [
     "tpsrhs_eval_pointwise", "tpsrhs_table_eval", "tpsrhs_math_eval", "tpsrhs_face_tables",
     "tpsrhs_rk4_step", "tpsrhs_advance", "tpsrhs_step", "tpsrhs_advance_with", "tpsrhs_set_dt", "tpsrhs_set_forcing", "tpsrhs_set_joule_heating", "tpsrhs_set_mixing_length", "tpsrhs_status_string",
     "tpsrhs_last_error", "tpsrhs_version",
+    "tpsrhs_stats_configure", "tpsrhs_stats_set_iter", "tpsrhs_stats_add_sample", "tpsrhs_stats_get", "tpsrhs_stats_set",
+    "tpsrhs_stats_num_variances",
 ]
 
 

@@ -69,6 +69,8 @@ const char *kKernelNames[NKERN] = {"k_traces", "k_gradient", "k_flux"};
 
 }  // namespace
 
+struct tpsrhs_stats_state;  // statistics.hpp: running mean and velocity covariances (tpsrhs.hip only)
+
 struct tpsrhs_operator {
   int dim = 0, order = 0, neq = 0, nvel = 0;
   int nc = 0;  // 1: the non-collocated Gauss-Lobatto pair (basisType 1, integrationRule 1), 0: the collocated Gauss-Legendre pair
@@ -158,6 +160,9 @@ struct tpsrhs_operator {
   bool sweep_alt = true;  // alternate the direction of consecutive sweeps (launch_all); TPSRHS_SWEEP_ALT
   int sweep_parity = 0;
   VsDev vs2d = {};  // viscous sponge of the 2-D heavy kernels (MeshDev::vs); enabled = 0: none
+  // tpsrhs_stats_configure; NULL: no statistics.  Owned by tpsrhs.hip (created, used and freed there: the kernel families
+  // never touch it).  Last member: nothing before it moves.
+  tpsrhs_stats_state *stats = nullptr;
 
   MeshDev mesh_dev() const {
     MeshDev m;

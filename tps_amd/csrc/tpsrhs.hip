@@ -8,6 +8,7 @@
 #include "physics_dryair_axisym.hpp"
 #include "physics_plasma.hpp"
 #include "plasma_params_host.hpp"
+#include "statistics.hpp"
 #include "time_integrators.hpp"
 
 #include <dlfcn.h>
@@ -640,6 +641,22 @@ int guarded(F &&f) {
   }
 }
 
+// Running statistics (statistics.hpp): at the end of this file
+void stats_release(tpsrhs_operator *h);
+void stats_sample(tpsrhs_operator *h, const double *x);
+// the time loop has taken one more step: count it and, at a sampling point, enqueue a sample of x
+inline void stats_after_step(tpsrhs_operator *h, const double *x) {
+  tpsrhs_stats_state *st = h->stats;
+  if (!st) return;
+  st->iter++;
+  if (st->iter % st->sample_interval == 0 && st->iter >= st->start_iter) stats_sample(h, x);
+}
+// would a sample fall after the first of the next two steps?
+inline bool stats_due_after_next(const tpsrhs_operator *h) {
+  const tpsrhs_stats_state *st = h->stats;
+  return st && (st->iter + 1) % st->sample_interval == 0 && st->iter + 1 >= st->start_iter;
+}
+
 }  // namespace
 
 #if TPSRHS_STAMP
@@ -665,6 +682,7 @@ int tpsrhs_create(const tpsrhs_mesh *mesh, const tpsrhs_disc *disc, const tpsrhs
 }
 
 int tpsrhs_destroy(tpsrhs_handle h) {
+  if (h) stats_release(h);
   delete h;
   return TPSRHS_OK;
 }
@@ -885,9 +903,12 @@ int advance_with(tpsrhs_handle h, int integrator, const char *who, double *x, do
     // (with forcing terms the stage kernel runs and nothing is fused; the other integrators never enter the trace chain)
     h->ta_chain = integrator == TPSRHS_RK4 && !h->forcing_active;
     try {
+      // Running statistics: the host issues every step anyway and knows the iteration number, so it enqueues the sample
+      // between two steps -- never inside the captured graph, whose key does not know about statistics.
       int step = 0;
       if (use_graph) {
         one_step();  // first step outside the graph: allocations, initial boundary state, its own k_traces sweep
+        stats_after_step(h, x);
         step = 1;
         tpsrhs_operator::StepKey key;
         key.x = x;
@@ -916,9 +937,23 @@ int advance_with(tpsrhs_handle h, int integrator, const char *who, double *x, do
           HIP_CHECK(ie);
           h->step_key = key;
         }
-        for (; step + steps_per_graph <= num_steps; step += steps_per_graph) HIP_CHECK(hipGraphLaunch(h->step_graph, h->stream));
+        for (; step + steps_per_graph <= num_steps; step += steps_per_graph) {
+          // a sample between the two steps of one graph: the pair runs as two plain steps (bit-equal to the replay, as the
+          // odd remainder below is), which leave the boundary-state buffers as the graph does
+          const bool split = steps_per_graph == 2 && stats_due_after_next(h);
+          for (int i = 0; i < steps_per_graph; i++) {
+            if (split)
+              one_step();
+            else if (i == 0)
+              HIP_CHECK(hipGraphLaunch(h->step_graph, h->stream));
+            stats_after_step(h, x);
+          }
+        }
       }
-      for (; step < num_steps; step++) one_step();
+      for (; step < num_steps; step++) {
+        one_step();
+        stats_after_step(h, x);
+      }
     } catch (...) {
       h->nr_dt_dev = nullptr;
       h->ta_chain = h->ta_valid = false;
@@ -1382,3 +1417,158 @@ void rk_stages(tpsrhs_operator *h, int integrator, double *x, double dt, const d
   }
 }
 }  // namespace
+
+// ---- running mean and velocity covariances (statistics.hpp) ----------------------------------------------------------------
+// After every other launch of this unit, as the integrators above.
+namespace {
+void stats_release(tpsrhs_operator *h) {
+  tpsrhs_stats_state *st = h->stats;
+  if (!st) return;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);  // a sample may still be running
+  for (double *p : {st->d_mean, st->d_vari, st->d_scratch})
+    if (p) (void)hipFree(p);
+  delete st;
+  h->stats = nullptr;
+}
+
+template <int NVEL, bool VARI>
+void launch_stats_sample(tpsrhs_operator *h) {
+  tpsrhs_stats_state *st = h->stats;
+  const int64_t n = h->ndofs;
+  const double *prim = st->d_scratch, *p = st->d_scratch + h->neq * n;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(prim) | reinterpret_cast<uintptr_t>(st->d_mean) | reinterpret_cast<uintptr_t>(st->d_vari);
+  const bool vec = (n & 1) == 0 && (bits & 15) == 0;  // then every row of every array is 16-byte aligned, p included
+  const int64_t items = vec ? n / 2 : n;
+  const int grid = static_cast<int>(std::min<int64_t>((items + 255) / 256, 8192));  // the grid cap of k_rk_stage
+  if (grid == 0) return;
+  if (vec)
+    hipLaunchKernelGGL((k_stats_sample<NVEL, VARI, true, 256>), dim3(grid), dim3(256), 0, h->stream, h->neq, n, st->ns_mean,
+                       st->ns_vari, prim, p, st->d_mean, st->d_vari);
+  else
+    hipLaunchKernelGGL((k_stats_sample<NVEL, VARI, false, 256>), dim3(grid), dim3(256), 0, h->stream, h->neq, n, st->ns_mean,
+                       st->ns_vari, prim, p, st->d_mean, st->d_vari);
+  HIP_CHECK(hipGetLastError());
+}
+
+// One sample of the device vector x, stream-ordered: the primitives and the pressure from the gas model's own point-wise
+// kernel (tpsrhs_eval_pointwise quantities 0 and 1: no physics here), then the update.  The counters are host integers.
+void stats_sample(tpsrhs_operator *h, const double *x) {
+  tpsrhs_stats_state *st = h->stats;
+  const int64_t n = h->ndofs;
+  h->point_eval(h, 0, n, x, st->d_scratch);
+  h->point_eval(h, 1, n, x, st->d_scratch + h->neq * n);
+  const bool vari = st->nvar > 0;
+  if (h->nvel == 3)
+    vari ? launch_stats_sample<3, true>(h) : launch_stats_sample<3, false>(h);
+  else
+    vari ? launch_stats_sample<2, true>(h) : launch_stats_sample<2, false>(h);
+  st->ns_mean++;
+  st->ns_vari++;
+}
+
+// the statistics of h, or NULL with the error text set
+tpsrhs_stats_state *stats_of(tpsrhs_handle h, const char *who) {
+  if (!h) {
+    fail(TPSRHS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL handle");
+    return nullptr;
+  }
+  if (!h->stats) fail(TPSRHS_ERR_INVALID_ARGUMENT, std::string(who) + ": statistics are not configured (tpsrhs_stats_configure)");
+  return h->stats;
+}
+}  // namespace
+
+extern "C" {
+
+int tpsrhs_stats_configure(tpsrhs_handle h, int64_t sample_interval, int64_t start_iter, int compute_variances) {
+  if (!h) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_configure: NULL handle");
+  if (sample_interval < 0 || start_iter < 0)
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_configure: needs sample_interval >= 0 (0: off) and start_iter >= 0");
+  if (sample_interval > 0 && h->nvel != 2 && h->nvel != 3)
+    return fail(TPSRHS_ERR_UNSUPPORTED, "tpsrhs_stats_configure: two or three velocity components");
+  return guarded([&] {
+    stats_release(h);
+    if (sample_interval == 0) return;
+    HIP_CHECK(hipSetDevice(h->device));
+    std::unique_ptr<tpsrhs_stats_state> st(new tpsrhs_stats_state());
+    st->sample_interval = sample_interval;
+    st->start_iter = start_iter;
+    st->nvar = compute_variances ? h->nvel * (h->nvel + 1) / 2 : 0;
+    const int64_t n = h->ndofs;
+    h->stats = st.release();  // from here on stats_release frees what was allocated
+    h->stats->d_mean = dev_alloc<double>(h->neq * n);
+    if (h->stats->nvar) h->stats->d_vari = dev_alloc<double>(h->stats->nvar * n);
+    h->stats->d_scratch = dev_alloc<double>((h->neq + 1) * n);
+    HIP_CHECK(hipMemsetAsync(h->stats->d_mean, 0, sizeof(double) * h->neq * n, h->stream));
+    if (h->stats->nvar) HIP_CHECK(hipMemsetAsync(h->stats->d_vari, 0, sizeof(double) * h->stats->nvar * n, h->stream));
+  });
+}
+
+int tpsrhs_stats_set_iter(tpsrhs_handle h, int64_t iter) {
+  tpsrhs_stats_state *st = stats_of(h, "tpsrhs_stats_set_iter");
+  if (!st) return TPSRHS_ERR_INVALID_ARGUMENT;
+  if (iter < 0) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_set_iter: needs iter >= 0");
+  st->iter = iter;
+  return TPSRHS_OK;
+}
+
+int tpsrhs_stats_add_sample(tpsrhs_handle h, const double *x) {
+  if (!stats_of(h, "tpsrhs_stats_add_sample")) return TPSRHS_ERR_INVALID_ARGUMENT;
+  if (!x) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_add_sample: NULL argument");
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(h->device));
+    stats_sample(h, x);
+  });
+}
+
+int tpsrhs_stats_get(tpsrhs_handle h, double *mean_out, double *vari_out, int *ns_mean, int *ns_vari, int64_t *iter) {
+  tpsrhs_stats_state *st = stats_of(h, "tpsrhs_stats_get");
+  if (!st) return TPSRHS_ERR_INVALID_ARGUMENT;
+  if (vari_out && !st->nvar)
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_get: the covariances are not computed (compute_variances = 0)");
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(h->device));
+    const int64_t n = h->ndofs;
+    if (mean_out) HIP_CHECK(hipMemcpyAsync(mean_out, st->d_mean, sizeof(double) * h->neq * n, hipMemcpyDeviceToDevice, h->stream));
+    if (vari_out) HIP_CHECK(hipMemcpyAsync(vari_out, st->d_vari, sizeof(double) * st->nvar * n, hipMemcpyDeviceToDevice, h->stream));
+    if (ns_mean) *ns_mean = st->ns_mean;
+    if (ns_vari) *ns_vari = st->ns_vari;
+    if (iter) *iter = st->iter;
+  });
+}
+
+int tpsrhs_stats_set(tpsrhs_handle h, const double *mean, const double *vari, int ns_mean, int ns_vari) {
+  tpsrhs_stats_state *st = stats_of(h, "tpsrhs_stats_set");
+  if (!st) return TPSRHS_ERR_INVALID_ARGUMENT;
+  if (ns_mean < 0 || ns_vari < 0 || (ns_mean > 0 && !mean))
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_set: needs counters >= 0 and the mean field of ns_mean > 0 samples");
+  if (vari && ns_vari > 0 && !st->nvar)
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_set: the covariances are not computed (compute_variances = 0)");
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(h->device));
+    const int64_t n = h->ndofs;
+    const bool keep_vari = vari && ns_vari > 0;  // else restartRMS: the covariances start again
+    if (ns_mean > 0)
+      HIP_CHECK(hipMemcpyAsync(st->d_mean, mean, sizeof(double) * h->neq * n, hipMemcpyDeviceToDevice, h->stream));
+    else
+      HIP_CHECK(hipMemsetAsync(st->d_mean, 0, sizeof(double) * h->neq * n, h->stream));
+    if (st->nvar) {
+      if (keep_vari)
+        HIP_CHECK(hipMemcpyAsync(st->d_vari, vari, sizeof(double) * st->nvar * n, hipMemcpyDeviceToDevice, h->stream));
+      else
+        HIP_CHECK(hipMemsetAsync(st->d_vari, 0, sizeof(double) * st->nvar * n, h->stream));
+    }
+    st->ns_mean = ns_mean;
+    st->ns_vari = keep_vari ? ns_vari : 0;
+  });
+}
+
+int tpsrhs_stats_num_variances(tpsrhs_handle h, int *num_variances) {
+  tpsrhs_stats_state *st = stats_of(h, "tpsrhs_stats_num_variances");
+  if (!st) return TPSRHS_ERR_INVALID_ARGUMENT;
+  if (!num_variances) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_num_variances: NULL argument");
+  *num_variances = st->nvar;
+  return TPSRHS_OK;
+}
+
+}  // extern "C"

@@ -197,6 +197,69 @@ class RHSoperator:
                 raise TpsRhsError(st, "tpsrhs_advance_with")
         return t.value, d.value, bad.value
 
+    # -- running statistics (the reference's Averaging) ------------------------------------------------------------------
+    def configureStatistics(self, sample_interval: int, start_iter: int = 0, variances: bool = True, iter0: int = 0):
+        """``Averaging`` inside :meth:`advance` (``src/averaging.cpp:198-234, 331-435``): after every step of ``advance``
+        the step counter goes up by one, and when it is a multiple of ``sample_interval`` (``sampleFreq``) and at least
+        ``start_iter`` (``startIter``) the new state enters the running mean of the primitives (pressure in the
+        temperature row) and, with ``variances``, the running velocity covariances.  ``iter0``: the step counter the
+        loop continues from.  ``sample_interval = 0`` switches statistics off and frees the fields."""
+        st = self._lib.tpsrhs_stats_configure(self._h, int(sample_interval), int(start_iter), 1 if variances else 0)
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_stats_configure")
+        if sample_interval != 0:
+            st = self._lib.tpsrhs_stats_set_iter(self._h, int(iter0))
+            if st != 0:
+                raise TpsRhsError(st, "tpsrhs_stats_set_iter")
+
+    def addSample(self, x: torch.Tensor):
+        """One unconditional sample of ``x`` (``Averaging::addSample`` for a caller that drives the loop itself);
+        asynchronous on the operator's stream."""
+        self._check(x)
+        st = self._lib.tpsrhs_stats_add_sample(self._h, C.c_void_p(x.data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_stats_add_sample")
+
+    def numVariances(self) -> int:
+        n = C.c_int(0)
+        st = self._lib.tpsrhs_stats_num_variances(self._h, C.byref(n))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_stats_num_variances")
+        return n.value
+
+    def getStatistics(self):
+        """``(mean, vari, ns_mean, ns_vari, iter)``: ``mean`` (num_equation, NDofs) and ``vari`` (nvar, NDofs; ``None``
+        when only the mean is kept) as new CUDA tensors -- the reference's ``meanUp`` and ``rms`` -- and its
+        ``samplesMean``, ``samplesRMS`` and ``iter``."""
+        nvar = self.numVariances()
+        mean = torch.empty(self.num_equation * self.NDofs, dtype=torch.float64, device=self.device)
+        vari = torch.empty(nvar * self.NDofs, dtype=torch.float64, device=self.device) if nvar else None
+        nm, nv, it = C.c_int(0), C.c_int(0), C.c_int64(0)
+        st = self._lib.tpsrhs_stats_get(self._h, C.c_void_p(mean.data_ptr()), C.c_void_p(vari.data_ptr()) if nvar else None,
+                                        C.byref(nm), C.byref(nv), C.byref(it))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_stats_get")
+        return (mean.view(self.num_equation, self.NDofs), vari.view(nvar, self.NDofs) if nvar else None, nm.value, nv.value,
+                it.value)
+
+    def setStatistics(self, mean, vari, ns_mean: int, ns_vari: int = 0, iter0=None):
+        """Continuation (``enableContinuation``): the fields and counters of an earlier run.  ``vari=None`` or
+        ``ns_vari=0`` is ``restartRMS``: the covariances start again and the mean goes on."""
+        for t, rows in ((mean, self.num_equation), (vari, None)):
+            if t is None:
+                continue
+            rows = self.numVariances() if rows is None else rows
+            if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.numel() != rows * self.NDofs:
+                raise ValueError(f"expected a contiguous float64 CUDA tensor of {rows} * NDofs entries")
+        st = self._lib.tpsrhs_stats_set(self._h, C.c_void_p(mean.data_ptr()) if mean is not None else None,
+                                        C.c_void_p(vari.data_ptr()) if vari is not None else None, int(ns_mean), int(ns_vari))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_stats_set")
+        if iter0 is not None:
+            st = self._lib.tpsrhs_stats_set_iter(self._h, int(iter0))
+            if st != 0:
+                raise TpsRhsError(st, "tpsrhs_stats_set_iter")
+
     def setDt(self, dt: float):
         """The ``dt`` the non-reflecting boundary conditions advance their boundary state with in every
         ``Mult`` (the reference's ``BoundaryCondition::dt`` is a reference to ``M2ulPhyS::dt``)."""
