@@ -503,6 +503,80 @@ int tpsrhs_stats_set(tpsrhs_handle h, const double *mean, const double *vari, in
 /* nvar, or 0 when only the mean is kept */
 int tpsrhs_stats_num_variances(tpsrhs_handle h, int *num_variances);
 
+/* ---- fields at arbitrary points: planes and probes ------------------------------------------------------------------
+ * What the reference's time loop does with the fields besides advancing and averaging them: it reads them where the user
+ * wants them.  `planeDump` (src/M2ulPhyS.cpp:2052-2096, options :2812-2831) interpolates the conserved state, the
+ * primitives, the mean or the Reynolds stresses onto an n x n plane through gslib's FindPointsGSLIB
+ * (src/gslib_interpolator.cpp:53-84) [third party: gslib, optional; without it the reference prints an error].  Here the
+ * operation is defined by the conventions at the top of this file and by nothing else:
+ *   - the nodal tensor Lagrange basis on the p + 1 Gauss-Legendre or Gauss-Lobatto nodes of [0,1] (tpsrhs_disc::basis_type),
+ *     l_a(t) = prod_{j != a} (t - x_j) / (x_a - x_j);  local = i + j*(p+1) + k*(p+1)^2;
+ *   - order-1 geometry: element e maps the reference cube [0,1]^dim to space by the bi-/trilinear map through its
+ *     elem_coords, MFEM vertex order (v0 at xi = 0; quad ccw; hex bottom ccw then top ccw).
+ * A point is LOCATED in an element when Newton's iteration on that map, started at the element centre (at most 50
+ * iterations), converges to reference coordinates that all lie in [-tol, 1 + tol]; they are not clamped.  A DG field has
+ * two values on a face: among the elements that accept a point the one with the LOWEST INDEX answers.  This is part of
+ * the contract.  A point no element accepts is "not found": element -1, reference coordinates 0, and `fill` as its value.
+ * Point arrays use the reference's layout, xyz[i + d*npts] (src/gslib_interpolator.cpp:97-104); sampled values are
+ * out[i + row*npts], the layout tpsrhs_eval_pointwise takes, so that sampled conserved states feed straight into it.
+ * Axisymmetric runs are plain 2-D in (r, z).
+ * Partitioned meshes: each rank locates, samples and records the points inside ITS OWN elements; elsewhere it reports
+ * "not found".  A point on a face shared by two ranks may be found by both.  Combining the ranks (the reference's gslib
+ * does it with its own MPI exchange) is the caller's job. */
+
+/* FindPointsGSLIB::Setup + FindPoints (src/gslib_interpolator.cpp:53-67).  Host only, touches no device (like
+ * tpsrhs_face_tables).  Candidates come from a uniform bin grid over the element bounding boxes, not from a sweep over the
+ * elements.  elem_out[npts]; ref_out[i + d*npts] in [0,1] (up to tol).  tol <= 0: 1e-10.  Both dim 2 and dim 3.
+ * NULL arguments, npts < 0, another dim: TPSRHS_ERR_INVALID_ARGUMENT. */
+int tpsrhs_locate_points(const tpsrhs_mesh *mesh, int64_t npts, const double *xyz, double tol, int32_t *elem_out,
+                         double *ref_out);
+/* PlaneInterpolator::setInterpolationPoints (src/gslib_interpolator.cpp:121-190), point for point: the n x n lattice over
+ * the bounding box [bb0, bb1] in the two directions other than the major direction of `normal` (the first of x, y, z with
+ * the largest |component|), i fastest and j slowest, the third coordinate from normal . (x - point) = 0.
+ * xyz_out: [3][n*n].  n < 2 or a NULL argument: TPSRHS_ERR_INVALID_ARGUMENT. */
+int tpsrhs_plane_points(const double point[3], const double normal[3], const double bb0[3], const double bb1[3], int n,
+                        double *xyz_out);
+
+typedef struct tpsrhs_sampler *tpsrhs_sampler_handle;
+
+/* FindPointsGSLIB::Setup + FindPoints on the operator's own (rank-local) mesh, order and basis (what
+ * PlaneInterpolator::initializeFinder + setInterpolationPoints leave behind, src/gslib_interpolator.cpp:53-67): xyz is a
+ * HOST array [dim][npts]; the element and reference coordinates of every point go to the device, sorted by element, with
+ * the permutation back to the caller's order.  fill: the value of points that were not found (FindPointsGSLIB's default
+ * is 0).  The operator OWNS its samplers: tpsrhs_destroy frees those that are left, and their handles die with it. */
+int tpsrhs_sampler_create(tpsrhs_handle h, int64_t npts, const double *xyz, double tol, double fill,
+                          tpsrhs_sampler_handle *out);
+/* Also switches the probes off when they record through this sampler.  NULL: nothing to do. */
+int tpsrhs_sampler_destroy(tpsrhs_sampler_handle s);
+/* FindPointsGSLIB::GetElem / GetReferencePosition / GetCode: HOST copies in the caller's order, elem_out[npts] (-1: not
+ * found) and ref_out[i + d*npts]; nfound the number of located points.  Any output may be NULL. */
+int tpsrhs_sampler_info(tpsrhs_sampler_handle s, int64_t *npts, int64_t *nfound, int32_t *elem_out, double *ref_out);
+/* FindPointsGSLIB::Interpolate (src/gslib_interpolator.cpp:69-84; the four field choices of planeDump,
+ * src/M2ulPhyS.cpp:2057-2087).  field: DEVICE, [nrows][NDofs], any byNODES array -- x, the output of tpsrhs_get_primitives,
+ * the mean and vari of tpsrhs_stats_get; out: DEVICE, [nrows][npts] in the caller's point order; points that were not found
+ * get `fill` in every row.  Asynchronous on the operator's stream.  nrows >= 1, no upper limit; a NULL argument or
+ * nrows < 1: TPSRHS_ERR_INVALID_ARGUMENT before any device work. */
+int tpsrhs_sample(tpsrhs_sampler_handle s, int nrows, const double *field, double *out);
+
+/* Probe time histories inside the device time loop (the per-iteration use of the interpolator: the reference calls its
+ * plane dump from solveStep, src/M2ulPhyS.cpp:2052-2096, on the host).  After
+ * every step of tpsrhs_advance / tpsrhs_advance_with a step counter goes up (tpsrhs_probe_configure zeroes it); when
+ * count % interval == 0 one record is enqueued between the steps:
+ *   values[record][num_equation][npts]  the conserved state x at the sampler's points (tpsrhs_sample of x)
+ *   times[record]                       the time, copied from DEVICE memory (the variable-dt loop never has it on the host)
+ *   iters[record]                       the count
+ * Nothing returns to the host; the record is never part of the captured step graph and never causes a re-capture.  When
+ * `capacity` records are held further records are dropped and counted: nothing is overwritten, nothing is written past the
+ * end.  tpsrhs_step and tpsrhs_rk4_step neither count nor record, as with the statistics.
+ * s == NULL or interval == 0 switches the probes off and frees the buffer; a negative value, capacity < 1 with probes on,
+ * or a sampler of another operator: TPSRHS_ERR_INVALID_ARGUMENT. */
+int tpsrhs_probe_configure(tpsrhs_handle h, tpsrhs_sampler_handle s, int64_t interval, int64_t capacity);
+/* Copies the held records to HOST arrays (iters_out[nrecords], times_out[nrecords], values_out[nrecords][neq][npts]) and
+ * synchronises the stream.  Any pointer may be NULL.  reset != 0 starts the buffer again (records and dropped count) and
+ * leaves the step counter alone.  Probes not configured: TPSRHS_ERR_INVALID_ARGUMENT. */
+int tpsrhs_probe_read(tpsrhs_handle h, int64_t *nrecords, int64_t *ndropped, int64_t *iters_out, double *times_out,
+                      double *values_out, int reset);
+
 /* The time step the non-reflecting boundary conditions integrate their boundary state with: the reference's
  * BoundaryCondition holds a reference to M2ulPhyS::dt (src/BoundaryCondition.hpp:54) and advances `boundaryU`
  * by dt in EVERY Mult (src/outletBC.cpp:712-724).  tpsrhs_rk4_step sets it itself. */

@@ -653,6 +653,15 @@ def load():
     lib.tpsrhs_stats_get.argtypes = [vp, vp, vp, _ip32, _ip32, C.POINTER(C.c_int64)]
     lib.tpsrhs_stats_set.argtypes = [vp, vp, vp, C.c_int, C.c_int]
     lib.tpsrhs_stats_num_variances.argtypes = [vp, _ip32]
+    _ip64 = C.POINTER(C.c_int64)
+    lib.tpsrhs_locate_points.argtypes = [C.POINTER(Mesh), C.c_int64, vp, C.c_double, vp, vp]
+    lib.tpsrhs_plane_points.argtypes = [_dp, _dp, _dp, _dp, C.c_int, vp]
+    lib.tpsrhs_sampler_create.argtypes = [vp, C.c_int64, vp, C.c_double, C.c_double, C.POINTER(vp)]
+    lib.tpsrhs_sampler_destroy.argtypes = [vp]
+    lib.tpsrhs_sampler_info.argtypes = [vp, _ip64, _ip64, vp, vp]
+    lib.tpsrhs_sample.argtypes = [vp, C.c_int, vp, vp]
+    lib.tpsrhs_probe_configure.argtypes = [vp, vp, C.c_int64, C.c_int64]
+    lib.tpsrhs_probe_read.argtypes = [vp, _ip64, _ip64, vp, vp, vp, C.c_int]
     lib.tpsrhs_set_dt.argtypes = [vp, C.c_double]
     lib.tpsrhs_set_forcing.argtypes = [vp, C.POINTER(Forcing)]
     lib.tpsrhs_set_joule_heating.argtypes = [vp, C.c_void_p]
@@ -676,6 +685,8 @@ EXPORTED_SYMBOLS = [
     "tpsrhs_last_error", "tpsrhs_version",
     "tpsrhs_stats_configure", "tpsrhs_stats_set_iter", "tpsrhs_stats_add_sample", "tpsrhs_stats_get", "tpsrhs_stats_set",
     "tpsrhs_stats_num_variances",
+    "tpsrhs_locate_points", "tpsrhs_plane_points", "tpsrhs_sampler_create", "tpsrhs_sampler_destroy", "tpsrhs_sampler_info",
+    "tpsrhs_sample", "tpsrhs_probe_configure", "tpsrhs_probe_read",
 ]
 
 

@@ -70,6 +70,7 @@ const char *kKernelNames[NKERN] = {"k_traces", "k_gradient", "k_flux"};
 }  // namespace
 
 struct tpsrhs_stats_state;  // statistics.hpp: running mean and velocity covariances (tpsrhs.hip only)
+struct tpsrhs_sampling_state;  // sampling.hpp: point samplers and probe records (tpsrhs.hip only)
 
 struct tpsrhs_operator {
   int dim = 0, order = 0, neq = 0, nvel = 0;
@@ -163,6 +164,9 @@ struct tpsrhs_operator {
   // tpsrhs_stats_configure; NULL: no statistics.  Owned by tpsrhs.hip (created, used and freed there: the kernel families
   // never touch it).  Last member: nothing before it moves.
   tpsrhs_stats_state *stats = nullptr;
+  // tpsrhs_sampler_create / tpsrhs_probe_configure; NULL: none yet.  The host copy of the element vertices, the samplers
+  // this operator owns and the probe buffer; owned by tpsrhs.hip like `stats`, and appended after it for the same reason.
+  tpsrhs_sampling_state *sampling = nullptr;
 
   MeshDev mesh_dev() const {
     MeshDev m;

@@ -8,6 +8,8 @@
 #include "physics_dryair_axisym.hpp"
 #include "physics_plasma.hpp"
 #include "plasma_params_host.hpp"
+#include "point_locate.hpp"
+#include "sampling.hpp"
 #include "statistics.hpp"
 #include "time_integrators.hpp"
 
@@ -656,6 +658,27 @@ inline bool stats_due_after_next(const tpsrhs_operator *h) {
   const tpsrhs_stats_state *st = h->stats;
   return st && (st->iter + 1) % st->sample_interval == 0 && st->iter + 1 >= st->start_iter;
 }
+// Probe records (sampling.hpp): at the end of this file
+void sampling_release(tpsrhs_operator *h);
+void probe_record(tpsrhs_operator *h, const double *x);
+// the same two questions for the probes: count the step and enqueue a record when one is due / is one due after the next step?
+inline void probe_after_step(tpsrhs_operator *h, const double *x) {
+  tpsrhs_sampling_state *ss = h->sampling;
+  if (!ss || !ss->probe) return;
+  ss->count++;
+  if (ss->count % ss->interval == 0) probe_record(h, x);
+}
+inline bool probe_due_after_next(const tpsrhs_operator *h) {
+  const tpsrhs_sampling_state *ss = h->sampling;
+  return ss && ss->probe && (ss->count + 1) % ss->interval == 0;
+}
+// What the time loop does between two steps, and whether any of it falls between the next two: everything that reads x
+// between steps goes through these two, so that the loop itself knows nothing about statistics or probes.
+inline void after_step(tpsrhs_operator *h, const double *x) {
+  stats_after_step(h, x);
+  probe_after_step(h, x);
+}
+inline bool work_due_after_next(const tpsrhs_operator *h) { return stats_due_after_next(h) || probe_due_after_next(h); }
 
 }  // namespace
 
@@ -683,6 +706,7 @@ int tpsrhs_create(const tpsrhs_mesh *mesh, const tpsrhs_disc *disc, const tpsrhs
 
 int tpsrhs_destroy(tpsrhs_handle h) {
   if (h) stats_release(h);
+  if (h) sampling_release(h);
   delete h;
   return TPSRHS_OK;
 }
@@ -903,12 +927,12 @@ int advance_with(tpsrhs_handle h, int integrator, const char *who, double *x, do
     // (with forcing terms the stage kernel runs and nothing is fused; the other integrators never enter the trace chain)
     h->ta_chain = integrator == TPSRHS_RK4 && !h->forcing_active;
     try {
-      // Running statistics: the host issues every step anyway and knows the iteration number, so it enqueues the sample
-      // between two steps -- never inside the captured graph, whose key does not know about statistics.
+      // Running statistics and probe records: the host issues every step anyway and knows the iteration number, so it
+      // enqueues the sample or the record between two steps -- never inside the captured graph, whose key knows about neither.
       int step = 0;
       if (use_graph) {
         one_step();  // first step outside the graph: allocations, initial boundary state, its own k_traces sweep
-        stats_after_step(h, x);
+        after_step(h, x);
         step = 1;
         tpsrhs_operator::StepKey key;
         key.x = x;
@@ -938,21 +962,21 @@ int advance_with(tpsrhs_handle h, int integrator, const char *who, double *x, do
           h->step_key = key;
         }
         for (; step + steps_per_graph <= num_steps; step += steps_per_graph) {
-          // a sample between the two steps of one graph: the pair runs as two plain steps (bit-equal to the replay, as the
-          // odd remainder below is), which leave the boundary-state buffers as the graph does
-          const bool split = steps_per_graph == 2 && stats_due_after_next(h);
+          // a sample or a record between the two steps of one graph: the pair runs as two plain steps (bit-equal to the
+          // replay, as the odd remainder below is), which leave the boundary-state buffers as the graph does
+          const bool split = steps_per_graph == 2 && work_due_after_next(h);
           for (int i = 0; i < steps_per_graph; i++) {
             if (split)
               one_step();
             else if (i == 0)
               HIP_CHECK(hipGraphLaunch(h->step_graph, h->stream));
-            stats_after_step(h, x);
+            after_step(h, x);
           }
         }
       }
       for (; step < num_steps; step++) {
         one_step();
-        stats_after_step(h, x);
+        after_step(h, x);
       }
     } catch (...) {
       h->nr_dt_dev = nullptr;
@@ -1569,6 +1593,245 @@ int tpsrhs_stats_num_variances(tpsrhs_handle h, int *num_variances) {
   if (!num_variances) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_num_variances: NULL argument");
   *num_variances = st->nvar;
   return TPSRHS_OK;
+}
+
+}  // extern "C"
+
+// ---- point sampling and probe records (sampling.hpp, point_locate.hpp) --------------------------------------------------------
+// After every other launch of this unit, as the integrators and the statistics above.
+namespace {
+void sampler_free(tpsrhs_sampler *s) {
+  if (s->d_elem) (void)hipFree(s->d_elem);
+  if (s->d_ref) (void)hipFree(s->d_ref);
+  if (s->d_perm) (void)hipFree(s->d_perm);
+  delete s;
+}
+
+void probe_off(tpsrhs_operator *h) {
+  tpsrhs_sampling_state *ss = h->sampling;
+  if (!ss) return;
+  if (ss->d_values || ss->d_times) {
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);  // a record may still be running
+    if (ss->d_values) (void)hipFree(ss->d_values);
+    if (ss->d_times) (void)hipFree(ss->d_times);
+  }
+  ss->d_values = ss->d_times = nullptr;
+  ss->probe = nullptr;
+  ss->interval = ss->capacity = ss->count = ss->nrecords = ss->ndropped = 0;
+  ss->iters.clear();
+}
+
+void sampling_release(tpsrhs_operator *h) {
+  tpsrhs_sampling_state *ss = h->sampling;
+  if (!ss) return;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);  // a sample may still be running
+  probe_off(h);
+  for (tpsrhs_sampler *s : ss->samplers) sampler_free(s);
+  delete ss;
+  h->sampling = nullptr;
+}
+
+template <int DIM, int P>
+void launch_sample(tpsrhs_operator *h, const tpsrhs_sampler *s, const SampleNodes &nodes, int nrows, const double *field,
+                   double *out) {
+  constexpr int BLOCK = 64;  // one wave: 64 probes are one block, a plane of 65 536 points is 1024 blocks over the 256 CUs
+  const int64_t grid = (s->npts + BLOCK - 1) / BLOCK;
+  if (grid == 0) return;
+  if (grid >= (int64_t(1) << 31)) throw Unsupported("tpsrhs_sample: more than 2^37 points");
+  hipLaunchKernelGGL((k_sample<DIM, P, BLOCK>), dim3(static_cast<unsigned>(grid)), dim3(BLOCK), 0, h->stream, s->npts, nrows,
+                     h->ndofs, nodes, s->d_elem, s->d_ref, s->d_perm, s->fill, field, out);
+  HIP_CHECK(hipGetLastError());
+}
+
+// out[nrows][npts] = field[nrows][NDofs] at the points of s, on the operator's stream
+void sample_field(tpsrhs_operator *h, const tpsrhs_sampler *s, int nrows, const double *field, double *out) {
+  SampleNodes nodes = {};
+  double wts[TPSRHS_MAXORDER + 1];
+  segment_rule01(h->nc, h->order + 1, nodes.x, wts);  // the nodes of the operator's basis, as make_tables places them
+  const int key = h->dim * 10 + h->order;
+  switch (key) {
+    case 21: launch_sample<2, 1>(h, s, nodes, nrows, field, out); break;
+    case 22: launch_sample<2, 2>(h, s, nodes, nrows, field, out); break;
+    case 23: launch_sample<2, 3>(h, s, nodes, nrows, field, out); break;
+    case 24: launch_sample<2, 4>(h, s, nodes, nrows, field, out); break;
+    case 25: launch_sample<2, 5>(h, s, nodes, nrows, field, out); break;
+    case 31: launch_sample<3, 1>(h, s, nodes, nrows, field, out); break;
+    case 32: launch_sample<3, 2>(h, s, nodes, nrows, field, out); break;
+    case 33: launch_sample<3, 3>(h, s, nodes, nrows, field, out); break;
+    case 34: launch_sample<3, 4>(h, s, nodes, nrows, field, out); break;
+    case 35: launch_sample<3, 5>(h, s, nodes, nrows, field, out); break;
+    default: throw Unsupported("tpsrhs_sample: dim 2 or 3 and polynomial orders 1..5 are built");
+  }
+}
+
+// One probe record of the device vector x, stream-ordered, or one more dropped record when the buffer is full.
+void probe_record(tpsrhs_operator *h, const double *x) {
+  tpsrhs_sampling_state *ss = h->sampling;
+  if (ss->nrecords >= ss->capacity) {
+    ss->ndropped++;
+    return;
+  }
+  const int64_t r = ss->nrecords, per = static_cast<int64_t>(h->neq) * ss->probe->npts;
+  sample_field(h, ss->probe, h->neq, x, ss->d_values + r * per);
+  HIP_CHECK(hipMemcpyAsync(ss->d_times + r, h->d_ctl + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  ss->iters.push_back(ss->count);
+  ss->nrecords++;
+}
+
+// is s a live sampler?  (its owner is then s->owner)
+bool sampler_alive(const tpsrhs_sampler *s, const tpsrhs_operator *h) {
+  const tpsrhs_sampling_state *ss = h ? h->sampling : nullptr;
+  return ss && std::find(ss->samplers.begin(), ss->samplers.end(), s) != ss->samplers.end();
+}
+}  // namespace
+
+extern "C" {
+
+int tpsrhs_locate_points(const tpsrhs_mesh *mesh, int64_t npts, const double *xyz, double tol, int32_t *elem_out,
+                         double *ref_out) {
+  const int st = locate_points(mesh, npts, xyz, tol, elem_out, ref_out);
+  if (st != TPSRHS_OK)
+    return fail(st, "tpsrhs_locate_points: needs a mesh of dim 2 or 3 with elem_coords, npts >= 0, non-NULL arrays and a tolerance that is a number");
+  return st;
+}
+
+int tpsrhs_plane_points(const double point[3], const double normal[3], const double bb0[3], const double bb1[3], int n,
+                        double *xyz_out) {
+  const int st = plane_points(point, normal, bb0, bb1, n, xyz_out);
+  if (st != TPSRHS_OK) return fail(st, "tpsrhs_plane_points: needs non-NULL arguments and n >= 2");
+  return st;
+}
+
+int tpsrhs_sampler_create(tpsrhs_handle h, int64_t npts, const double *xyz, double tol, double fill,
+                          tpsrhs_sampler_handle *out) {
+  if (out) *out = nullptr;
+  if (!h || !out || npts < 0 || (npts > 0 && !xyz) || std::isnan(tol))
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_sampler_create: needs a handle, npts >= 0, the points and a tolerance that is a number");
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(h->device));
+    const int dim = h->dim;
+    std::unique_ptr<tpsrhs_sampler> sp(new tpsrhs_sampler());
+    sp->owner = h;
+    sp->npts = npts;
+    sp->fill = fill;
+    sp->elem.assign(static_cast<size_t>(npts), -1);
+    sp->ref.assign(static_cast<size_t>(npts) * dim, 0.0);
+    // the operator's own host copy of the element vertices (Topology::verts, already in lexicographic corner order)
+    const double t = tol > 0.0 ? tol : LOCATE_DEFAULT_TOL;
+    if (dim == 2)
+      locate_points_lex<2>(h->ne, h->topo.verts.data(), npts, xyz, t, sp->elem.data(), sp->ref.data());
+    else
+      locate_points_lex<3>(h->ne, h->topo.verts.data(), npts, xyz, t, sp->elem.data(), sp->ref.data());
+    // sorted by element, ties in the caller's order, the points that were not found last
+    std::vector<int64_t> perm(static_cast<size_t>(npts));
+    for (int64_t i = 0; i < npts; i++) perm[static_cast<size_t>(i)] = i;
+    const std::vector<int32_t> &el = sp->elem;
+    std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) {
+      const int64_t ea = el[static_cast<size_t>(a)] < 0 ? int64_t(1) << 40 : el[static_cast<size_t>(a)];
+      const int64_t eb = el[static_cast<size_t>(b)] < 0 ? int64_t(1) << 40 : el[static_cast<size_t>(b)];
+      return ea < eb;
+    });
+    std::vector<int32_t> selem(static_cast<size_t>(npts));
+    std::vector<double> sref(static_cast<size_t>(npts) * dim);
+    for (int64_t k = 0; k < npts; k++) {
+      const int64_t i = perm[static_cast<size_t>(k)];
+      selem[static_cast<size_t>(k)] = el[static_cast<size_t>(i)];
+      if (el[static_cast<size_t>(i)] >= 0) sp->nfound++;
+      for (int d = 0; d < dim; d++) sref[static_cast<size_t>(k + d * npts)] = sp->ref[static_cast<size_t>(i + d * npts)];
+    }
+    tpsrhs_sampler *s = sp.release();
+    struct Guard {
+      tpsrhs_sampler *s;
+      ~Guard() {
+        if (s) sampler_free(s);
+      }
+    } guard{s};
+    s->d_elem = dev_upload(selem);
+    s->d_ref = dev_upload(sref);
+    s->d_perm = dev_upload(perm);
+    if (!h->sampling) h->sampling = new tpsrhs_sampling_state();
+    h->sampling->samplers.push_back(s);
+    guard.s = nullptr;
+    *out = s;
+  });
+}
+
+int tpsrhs_sampler_destroy(tpsrhs_sampler_handle s) {
+  if (!s) return TPSRHS_OK;
+  tpsrhs_operator *h = s->owner;
+  if (!sampler_alive(s, h)) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_sampler_destroy: not a sampler of a live operator");
+  tpsrhs_sampling_state *ss = h->sampling;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);  // a sample may still be running
+  if (ss->probe == s) probe_off(h);
+  ss->samplers.erase(std::find(ss->samplers.begin(), ss->samplers.end(), s));
+  sampler_free(s);
+  return TPSRHS_OK;
+}
+
+int tpsrhs_sampler_info(tpsrhs_sampler_handle s, int64_t *npts, int64_t *nfound, int32_t *elem_out, double *ref_out) {
+  if (!s) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_sampler_info: NULL sampler");
+  if (npts) *npts = s->npts;
+  if (nfound) *nfound = s->nfound;
+  if (elem_out && s->npts) std::memcpy(elem_out, s->elem.data(), s->elem.size() * sizeof(int32_t));
+  if (ref_out && s->npts) std::memcpy(ref_out, s->ref.data(), s->ref.size() * sizeof(double));
+  return TPSRHS_OK;
+}
+
+int tpsrhs_sample(tpsrhs_sampler_handle s, int nrows, const double *field, double *out) {
+  if (!s || !field || !out || nrows < 1)
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_sample: needs a sampler, nrows >= 1 and non-NULL device arrays");
+  tpsrhs_operator *h = s->owner;
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(h->device));
+    sample_field(h, s, nrows, field, out);
+  });
+}
+
+int tpsrhs_probe_configure(tpsrhs_handle h, tpsrhs_sampler_handle s, int64_t interval, int64_t capacity) {
+  if (!h) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_probe_configure: NULL handle");
+  if (interval < 0 || capacity < 0)
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_probe_configure: needs interval >= 0 (0: off) and capacity >= 0");
+  const bool on = s != nullptr && interval > 0;
+  if (on && capacity < 1) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_probe_configure: needs capacity >= 1");
+  if (on && (s->owner != h || !sampler_alive(s, h)))
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_probe_configure: the sampler belongs to another operator");
+  return guarded([&] {
+    probe_off(h);
+    if (!on) return;
+    HIP_CHECK(hipSetDevice(h->device));
+    tpsrhs_sampling_state *ss = h->sampling;  // exists: s is one of its samplers
+    ss->d_values = dev_alloc<double>(capacity * h->neq * s->npts);
+    ss->d_times = dev_alloc<double>(capacity);
+    if (!h->d_ctl) h->d_ctl = dev_alloc<double>(3);  // the loop's {dt, time, max speed}: a record copies the time from there
+    ss->probe = s;
+    ss->interval = interval;
+    ss->capacity = capacity;
+  });
+}
+
+int tpsrhs_probe_read(tpsrhs_handle h, int64_t *nrecords, int64_t *ndropped, int64_t *iters_out, double *times_out,
+                      double *values_out, int reset) {
+  if (!h) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_probe_read: NULL handle");
+  tpsrhs_sampling_state *ss = h->sampling;
+  if (!ss || !ss->probe) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_probe_read: probes are not configured (tpsrhs_probe_configure)");
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(h->device));
+    const int64_t n = ss->nrecords, per = static_cast<int64_t>(h->neq) * ss->probe->npts;
+    if (times_out && n) HIP_CHECK(hipMemcpyAsync(times_out, ss->d_times, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+    if (values_out && n * per)
+      HIP_CHECK(hipMemcpyAsync(values_out, ss->d_values, sizeof(double) * n * per, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (nrecords) *nrecords = n;
+    if (ndropped) *ndropped = ss->ndropped;
+    if (iters_out && n) std::memcpy(iters_out, ss->iters.data(), sizeof(int64_t) * n);
+    if (reset) {  // the buffer starts again; the step counter goes on
+      ss->nrecords = ss->ndropped = 0;
+      ss->iters.clear();
+    }
+  });
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@ GPU raises -- there is no CPU path.
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 
 import numpy as np
 import torch
@@ -260,6 +261,42 @@ class RHSoperator:
             if st != 0:
                 raise TpsRhsError(st, "tpsrhs_stats_set_iter")
 
+    # -- fields at arbitrary points: planes and probes ----------------------------------------------------------------------
+    def createSampler(self, xyz, tol: float = 0.0, fill: float = 0.0) -> "PointSampler":
+        """``FindPointsGSLIB::Setup`` + ``FindPoints`` on this operator's mesh (``src/gslib_interpolator.cpp:53-67``):
+        ``xyz`` is a host array ``(dim, npts)``; ``tol <= 0`` is 1e-10; ``fill`` is the value of points outside the mesh.
+        The operator owns the sampler: closing the operator closes it."""
+        s = PointSampler(self, xyz, tol, fill)
+        self._samplers = [w for w in getattr(self, "_samplers", []) if w() is not None] + [weakref.ref(s)]
+        return s
+
+    def configureProbes(self, sampler, interval: int, capacity: int):
+        """Probe records inside :meth:`advance`: after every step a counter goes up (zeroed here), and when it is a
+        multiple of ``interval`` the conserved state at the sampler's points, the device-side time and the count are
+        appended to a device buffer of ``capacity`` records; further records are dropped and counted.
+        ``sampler=None`` or ``interval=0`` switches the probes off."""
+        st = self._lib.tpsrhs_probe_configure(self._h, sampler._s if sampler is not None else None, int(interval), int(capacity))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_probe_configure")
+        self._probe = (sampler, int(capacity)) if sampler is not None and interval != 0 else None
+
+    def readProbes(self, reset: bool = False):
+        """``(iters (nrec,), times (nrec,), values (nrec, num_equation, npts), ndropped)`` as numpy arrays; synchronises.
+        ``reset`` starts the buffer again and leaves the step counter alone."""
+        if getattr(self, "_probe", None) is None:
+            raise TpsRhsError(self._lib.tpsrhs_probe_read(self._h, None, None, None, None, None, 0), "tpsrhs_probe_read")
+        sampler, capacity = self._probe
+        iters = np.zeros(capacity, dtype=np.int64)
+        times = np.zeros(capacity)
+        values = np.zeros((capacity, self.num_equation, sampler.npts))
+        nrec, ndrop = C.c_int64(0), C.c_int64(0)
+        st = self._lib.tpsrhs_probe_read(self._h, C.byref(nrec), C.byref(ndrop), iters.ctypes.data, times.ctypes.data,
+                                         values.ctypes.data, 1 if reset else 0)
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_probe_read")
+        n = nrec.value
+        return iters[:n].copy(), times[:n].copy(), values[:n].copy(), ndrop.value
+
     def setDt(self, dt: float):
         """The ``dt`` the non-reflecting boundary conditions advance their boundary state with in every
         ``Mult`` (the reference's ``BoundaryCondition::dt`` is a reference to ``M2ulPhyS::dt``)."""
@@ -314,6 +351,10 @@ class RHSoperator:
 
     def close(self):
         if getattr(self, "_h", None):
+            for w in getattr(self, "_samplers", []):  # tpsrhs_destroy frees them: their handles die here
+                if w() is not None:
+                    w()._s = None
+            self._probe = None
             self._lib.tpsrhs_destroy(self._h)
             self._h = None
 
@@ -322,6 +363,91 @@ class RHSoperator:
             self.close()
         except Exception:
             pass
+
+
+class PointSampler:
+    """A set of points located in one operator's mesh (``tpsrhs_sampler_*``): the reference's ``InterpolatorBase`` after
+    ``initializeFinder`` and ``setInterpolationPoints`` (``src/gslib_interpolator.cpp:53-67``)."""
+
+    def __init__(self, op: RHSoperator, xyz, tol: float = 0.0, fill: float = 0.0):
+        self._lib = capi.load()
+        self._op = op
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        if xyz.ndim != 2 or xyz.shape[0] != op.dim:
+            raise ValueError("expected the points as an array (dim, npts)")
+        self.npts = int(xyz.shape[1])
+        s = C.c_void_p()
+        st = self._lib.tpsrhs_sampler_create(op._h, self.npts, xyz.ctypes.data, float(tol), float(fill), C.byref(s))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_sampler_create")
+        self._s = s
+
+    def info(self):
+        """``(elem (npts,), ref (dim, npts), nfound)``: the element of every point (-1: not found) and its reference
+        coordinates in [0,1], in the caller's order."""
+        elem = np.zeros(self.npts, dtype=np.int32)
+        ref = np.zeros((self._op.dim, self.npts))
+        n, nf = C.c_int64(0), C.c_int64(0)
+        st = self._lib.tpsrhs_sampler_info(self._s, C.byref(n), C.byref(nf), elem.ctypes.data, ref.ctypes.data)
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_sampler_info")
+        return elem, ref, nf.value
+
+    def sample(self, field: torch.Tensor) -> torch.Tensor:
+        """``FindPointsGSLIB::Interpolate`` (``src/gslib_interpolator.cpp:69-84``): ``field`` is a float64 CUDA tensor of
+        ``nrows * NDofs`` entries (byNODES); returns ``(nrows, npts)``.  Asynchronous on the operator's stream."""
+        n = self._op.NDofs
+        if field.dtype != torch.float64 or not field.is_cuda or not field.is_contiguous() or field.numel() % n or not field.numel():
+            raise ValueError("expected a contiguous float64 CUDA tensor of nrows * NDofs entries")
+        nrows = field.numel() // n
+        out = torch.empty((nrows, self.npts), dtype=torch.float64, device=field.device)
+        if self.npts == 0:
+            return out
+        st = self._lib.tpsrhs_sample(self._s, nrows, C.c_void_p(field.data_ptr()), C.c_void_p(out.data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_sample")
+        return out
+
+    def close(self):
+        if getattr(self, "_s", None):
+            if getattr(self._op, "_probe", None) is not None and self._op._probe[0] is self:
+                self._op._probe = None
+            self._lib.tpsrhs_sampler_destroy(self._s)
+        self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def locate_points(host_mesh, xyz, tol: float = 0.0):
+    """Host-only call of ``tpsrhs_locate_points``: ``xyz`` ``(dim, npts)`` -> ``(elem (npts,), ref (dim, npts))``."""
+    lib = capi.load()
+    ma = capi.MeshArgs(host_mesh)
+    xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+    if xyz.ndim != 2 or xyz.shape[0] != host_mesh.dim:
+        raise ValueError("expected the points as an array (dim, npts)")
+    npts = xyz.shape[1]
+    elem = np.zeros(npts, dtype=np.int32)
+    ref = np.zeros((host_mesh.dim, npts))
+    st = lib.tpsrhs_locate_points(C.byref(ma.c), npts, xyz.ctypes.data, float(tol), elem.ctypes.data, ref.ctypes.data)
+    if st != 0:
+        raise TpsRhsError(st, "tpsrhs_locate_points")
+    return elem, ref
+
+
+def plane_points(point, normal, bb0, bb1, n: int) -> np.ndarray:
+    """``PlaneInterpolator::setInterpolationPoints`` (``src/gslib_interpolator.cpp:121-190``): the ``(3, n*n)`` points of
+    the plane through ``point`` with ``normal`` over the bounding box ``[bb0, bb1]``."""
+    lib = capi.load()
+    a = [(C.c_double * 3)(*[float(v) for v in w]) for w in (point, normal, bb0, bb1)]
+    out = np.zeros((3, max(int(n), 0) ** 2))
+    st = lib.tpsrhs_plane_points(a[0], a[1], a[2], a[3], int(n), out.ctypes.data)
+    if st != 0:
+        raise TpsRhsError(st, "tpsrhs_plane_points")
+    return out
 
 
 def node_coordinates(host_mesh, order: int, basis_type: int = 0) -> np.ndarray:
