@@ -657,6 +657,52 @@ typedef struct tpsrhs_mixing_length { /* mixingLengthTransportData (src/dataStru
 } tpsrhs_mixing_length;
 int tpsrhs_set_mixing_length(tpsrhs_handle h, const double *distance, const tpsrhs_mixing_length *params);
 
+/* ---- the wall-distance function (flow/computeDistance) -----------------------------------------------------------------
+ * What the reference computes once at start-up when `flow/computeDistance` is set (src/M2ulPhyS.cpp:371-437, every input
+ * with useMixingLength sets it): the distance from every DG node to the nearest wall boundary face,
+ * evaluateDistanceSerial (src/utils.cpp:371-514) -- there one serial host loop over nodes x wall faces; here the faces are
+ * selected on the host (tpsrhs_wall_faces) and the all-pairs search runs on the device (tpsrhs_wall_distance).  The result
+ * is the `distance` array tpsrhs_set_mixing_length takes.  The operation, defined by the conventions at the top of this file:
+ *   - the node coordinates xp are those of the DG nodes under the order-1 geometry: the bi-/trilinear map through
+ *     elem_coords at the tensor Gauss-Legendre / Gauss-Lobatto nodes of the operator (the reference's `coordinates` grid
+ *     function after SetCurvature(1)).  Axisymmetric runs are plain 2-D in (r, z).
+ *   - a wall face is the straight segment (2-D) or the bilinear quadrilateral (3-D) through its 2 / 4 corners, X(xi) on
+ *     [0,1]^(dim-1); corner = ta + 2 tb.
+ *   - per (node, face): start at the centre xi = 1/2; dx = xp - X(xi), res = -J^T dx with J = dX/dxi (dim x (dim-1)),
+ *     r0 = |res|; while (|res| > 1e-16 && |res| / r0 > 1e-10 && iter < 20): xi += (J^T J)^{-1} J^T dx (the Hessian of the
+ *     map is neglected, as in the reference) and dx, res are formed again; with r0 == 0 the loop is skipped.  Then every
+ *     coordinate of xi is clamped to [0,1] [third party: MFEM Geometry::CheckPoint / ProjectPoint for SEGMENT and SQUARE]
+ *     and the distance to the face is |xp - X(xi)|.
+ *   - distance[node] = the minimum over the faces, kept with `<`, starting from 1e30: without a wall face every entry is
+ *     1e30, and a NaN distance (a collapsed face) never wins.
+ * The orientation of a face does not matter (the iteration and the clamp are invariant under the symmetries of the
+ * reference square).  The reference prints a warning when the iteration stops at its cap; NOTHING corresponds to it here,
+ * on purpose: for affine faces Newton lands in one step and the warning then fires whenever r0 itself is at rounding
+ * level, so its count is rounding noise and no part of a contract.  Curved (order > 1) geometry is not built. */
+
+/* Host only, touches no device (like tpsrhs_face_tables and tpsrhs_locate_points): the corner coordinates of the wall
+ * boundary faces of `mesh`.  num_attributes >= 0: the boundary faces whose attribute is in `attributes` (bcs may be
+ * NULL).  num_attributes < 0: the reference's rule (src/M2ulPhyS.cpp:392-398) -- every entry of `bcs` of category
+ * TPSRHS_WALL whose type is not TPSRHS_INV.  face_xyz_out[face][corner][dim], corner = ta + 2 tb of the owning element's
+ * local face (2^(dim-1) corners), coordinates from the owning element's elem_coords (periodic meshes keep their geometry);
+ * faces in ascending (element, local face) order.  *num_faces_out is always the full count; min(count, capacity) faces are
+ * written, and face_xyz_out may be NULL with capacity == 0.  A boundary record that matches no element face, a NULL mesh,
+ * a dim other than 2 / 3, a negative capacity or a missing array: TPSRHS_ERR_INVALID_ARGUMENT. */
+int tpsrhs_wall_faces(const tpsrhs_mesh *mesh, int num_bcs, const tpsrhs_bc *bcs, int num_attributes, const int *attributes,
+                      int64_t capacity, double *face_xyz_out, int64_t *num_faces_out);
+
+/* distance_out[NDofs] (DEVICE) = the wall distance of every node of the operator to the num_faces faces of face_xyz (HOST,
+ * the layout of tpsrhs_wall_faces, dim = the operator's).  Ordered on the operator's stream, which is synchronised before
+ * the call returns (a start-up function: its temporary face table on the device is freed then); every entry of
+ * distance_out is written, also for num_faces == 0 (1e30).  Divisions and square roots are IEEE (correctly rounded).
+ * Partitioned meshes: a rank's nodes need the wall faces of ALL ranks (the reference computes on the serial mesh): every
+ * rank calls tpsrhs_wall_faces on its own mesh and the caller concatenates the lists (an all-gather) -- the caller's job,
+ * as with the samplers.  num_faces < 0, a NULL handle or output, NULL faces with num_faces > 0 or a face coordinate that is
+ * not finite: TPSRHS_ERR_INVALID_ARGUMENT before any device work.  TPSRHS_WALLDIST_CULL=0 (environment, read per call)
+ * switches off the conservative cull -- a face whose bounding sphere lies farther from the node than the best distance so
+ * far cannot win the minimum and is skipped; the results are bit-equal either way. */
+int tpsrhs_wall_distance(tpsrhs_handle h, int64_t num_faces, const double *face_xyz, double *distance_out);
+
 /* JouleHeating (src/forcing_terms.cpp:443-471): `joule_heating` is the DEVICE array of the
  * `joule_heating_` grid function (NDofs doubles, owned by the caller, read at every Mult; the EM solver
  * refreshes it between steps).  Positive entries are added to the total-energy equation and, for a

@@ -662,6 +662,8 @@ def load():
     lib.tpsrhs_sample.argtypes = [vp, C.c_int, vp, vp]
     lib.tpsrhs_probe_configure.argtypes = [vp, vp, C.c_int64, C.c_int64]
     lib.tpsrhs_probe_read.argtypes = [vp, _ip64, _ip64, vp, vp, vp, C.c_int]
+    lib.tpsrhs_wall_faces.argtypes = [C.POINTER(Mesh), C.c_int, C.POINTER(BC), C.c_int, vp, C.c_int64, vp, _ip64]
+    lib.tpsrhs_wall_distance.argtypes = [vp, C.c_int64, vp, vp]
     lib.tpsrhs_set_dt.argtypes = [vp, C.c_double]
     lib.tpsrhs_set_forcing.argtypes = [vp, C.POINTER(Forcing)]
     lib.tpsrhs_set_joule_heating.argtypes = [vp, C.c_void_p]
@@ -687,6 +689,7 @@ EXPORTED_SYMBOLS = [
     "tpsrhs_stats_num_variances",
     "tpsrhs_locate_points", "tpsrhs_plane_points", "tpsrhs_sampler_create", "tpsrhs_sampler_destroy", "tpsrhs_sampler_info",
     "tpsrhs_sample", "tpsrhs_probe_configure", "tpsrhs_probe_read",
+    "tpsrhs_wall_faces", "tpsrhs_wall_distance",
 ]
 
 
@@ -708,3 +711,32 @@ def face_tables(host_mesh, bcs=()):
         raise RuntimeError(f"tpsrhs_face_tables: {lib.tpsrhs_status_string(st).decode()}: "
                            f"{lib.tpsrhs_last_error().decode()}")
     return fn.reshape(ne, nlf), fo.reshape(ne, nlf), ss[:ns], so[:ns]
+
+
+def wall_faces(host_mesh, bcs=(), attributes=None) -> np.ndarray:
+    """Host-only call of ``tpsrhs_wall_faces``: the corner coordinates ``(nf, 2^(dim-1), dim)`` of the wall boundary faces
+    of ``host_mesh``, corner = ta + 2 tb of the owning element's local face, in ascending (element, local face) order.
+    ``attributes``: the boundary attributes that count as walls; ``None`` is the reference's rule
+    (``src/M2ulPhyS.cpp:392-398``): every entry of ``bcs`` of category WALL whose type is not INV."""
+    lib = load()
+    ma = MeshArgs(host_mesh)
+    dim = host_mesh.dim
+    arr = (BC * max(1, len(bcs)))(*bcs)
+    if attributes is None:
+        natt, att = -1, None
+    else:
+        att = np.ascontiguousarray(attributes, dtype=np.int32).ravel()
+        natt = int(att.size)
+    n = C.c_int64(0)
+
+    def call(capacity, out):
+        st = lib.tpsrhs_wall_faces(C.byref(ma.c), len(bcs), arr, natt, att.ctypes.data if att is not None and natt else None,
+                                   capacity, out.ctypes.data if out is not None else None, C.byref(n))
+        if st != 0:
+            raise RuntimeError(f"tpsrhs_wall_faces: {lib.tpsrhs_status_string(st).decode()}: {lib.tpsrhs_last_error().decode()}")
+
+    call(0, None)  # the count
+    out = np.zeros((n.value, 1 << (dim - 1), dim))
+    if n.value:
+        call(n.value, out)
+    return out

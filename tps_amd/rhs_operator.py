@@ -42,6 +42,7 @@ class RHSoperator:
         self.device = torch.device("cuda", device)
         self._margs = capi.MeshArgs(host_mesh)
         self._disc, self._physics = disc, physics
+        self._mesh, self._bc_list = host_mesh, list(bcs)
         self._bcs = (capi.BC * max(1, len(bcs)))(*bcs)
         rt = capi.Runtime()
         rt.device = device
@@ -338,6 +339,27 @@ class RHSoperator:
                                                 C.byref(prm))
         if st != 0:
             raise TpsRhsError(st, "tpsrhs_set_mixing_length")
+
+    def wallDistance(self, faces=None, attributes=None) -> torch.Tensor:
+        """The wall-distance grid function ``distance_`` the reference fills at start-up when ``flow/computeDistance`` is set
+        (``evaluateDistanceSerial``, ``src/utils.cpp:371-514``): the distance from every node to the nearest of ``faces``
+        (``(nf, 2^(dim-1), dim)`` corner coordinates, :func:`tps_amd.capi.wall_faces`), a new float64 CUDA tensor of NDofs
+        entries -- what :meth:`setMixingLength` takes.  ``faces=None``: the wall faces of the operator's own mesh, selected
+        by ``attributes`` or, with ``attributes=None``, by its boundary conditions (every wall that is not inviscid).  On a
+        partitioned mesh pass the concatenation of the wall faces of all ranks.  Without faces every entry is 1e30."""
+        if faces is None:
+            faces = capi.wall_faces(self._mesh, self._bc_list, attributes)
+        faces = np.ascontiguousarray(faces, dtype=np.float64)
+        if faces.size == 0:
+            faces = faces.reshape(0, 1 << (self.dim - 1), self.dim)
+        if faces.ndim != 3 or faces.shape[1:] != (1 << (self.dim - 1), self.dim):
+            raise ValueError("expected the faces as an array (nf, 2^(dim-1), dim)")
+        out = torch.empty(self.NDofs, dtype=torch.float64, device=self.device)
+        st = self._lib.tpsrhs_wall_distance(self._h, int(faces.shape[0]), faces.ctypes.data if faces.size else None,
+                                            C.c_void_p(out.data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_wall_distance")
+        return out
 
     def kernel_bytes(self):
         names = (C.c_char_p * 8)()
