@@ -703,6 +703,66 @@ int tpsrhs_wall_faces(const tpsrhs_mesh *mesh, int num_bcs, const tpsrhs_bc *bcs
  * far cannot win the minimum and is skipped; the results are bit-equal either way. */
 int tpsrhs_wall_distance(tpsrhs_handle h, int64_t num_faces, const double *face_xyz, double *distance_out);
 
+/* ---- volume integrals, L2 errors, extrema and the monitor history of the time loop ------------------------------------
+ * The global numbers a solver's time loop reports: the conserved totals, the range of every state variable, the L2 error
+ * against a known solution -- M2ulPhyS::checkSolutionError (src/masa_handler.cpp:139-152) through
+ * GridFunction::ComputeLpError(2, ...) [third party: MFEM, fem/gridfunc.cpp; its default rule is Gauss-Legendre of order
+ * 2p + 3] -- the mean |dU/dt| per equation (RHSoperator::computeMeanTimeDerivatives, src/rhs_operator.cpp:833-849) and the
+ * step-size history, which with a variable step exists only in device memory.  All are reductions over a byNODES field.
+ * THE RULE, part of the contract:
+ *   - tensor Gauss-Legendre with NQ = p + 2 points per direction on [0,1] (MFEM's order 2p + 3), points numbered
+ *     q = e*NQ^dim + (i + j*NQ + k*NQ^2);
+ *   - order-1 geometry, as for the samplers: the bi-/trilinear map through elem_coords;
+ *   - W_q = w_i w_j (w_k) |det J(xi_q)|, and with radial_weight != 0  W_q r_q, r_q the FIRST coordinate of the mapped
+ *     point (the axisymmetric formulation's (r, z)); there is no factor 2 pi;
+ *   - a nodal field is evaluated at the points with the operator's Lagrange basis (Gauss-Legendre or Gauss-Lobatto
+ *     nodes), one direction after the other (sum factorisation).
+ * The rule is exact for f_h, for f_h^2 and for both times det J of a trilinear hexahedron (degree <= 2p + 2 per direction).
+ * SUMMATION STRUCTURE, part of the contract: the terms of one element are summed first, the element sums are combined in
+ * a fixed order, and a last single-block kernel reads the per-block partials.  No floating-point atomics: two calls on
+ * the same input give the same bits.  With K = NQ^dim + ne + 8 dim (p+1) the rounding error of `sum` is at most
+ * K eps sum_q W_q A_q and that of `sumsq` at most 2 K eps sum_q W_q (A_q + |exact_q|)^2, A_q = sum_n |l_n(xi_q)| |f_n|.
+ * Partitioned meshes: every rank reduces its own elements and the caller combines the ranks, as with the samplers. */
+
+/* Host only, touches no device: the points and weights of the rule on `mesh` for polynomial order `order`.
+ * xyz_out[d*npts + q] (the layout of tpsrhs_locate_points), w_out[q] = W_q WITHOUT the radial factor; either may be NULL;
+ * *npts_out = num_elements * NQ^dim is always written.  A NULL mesh or npts_out, a dim other than 2 / 3 or an order outside
+ * 1 ... TPSRHS_MAXORDER: TPSRHS_ERR_INVALID_ARGUMENT. */
+int tpsrhs_quadrature_points(const tpsrhs_mesh *mesh, int order, double *xyz_out, double *w_out, int64_t *npts_out);
+
+/* g_q = f_h(xi_q) - exact_q[row][q] (exact_q == NULL counts as 0):  sum_out[row] = sum_q W_q g_q,
+ * sumsq_out[row] = sum_q W_q g_q^2 -- sqrt(sumsq) is ComputeLpError(2, .).  field: DEVICE [nrows][NDofs], any byNODES
+ * array; exact_q: DEVICE [nrows][npts] at the points of tpsrhs_quadrature_points, or NULL; the outputs: DEVICE [nrows],
+ * either may be NULL.  Asynchronous on the operator's stream; the field is read once.  nrows >= 1, no upper limit; a NULL
+ * handle or field, or nrows < 1: TPSRHS_ERR_INVALID_ARGUMENT before any device work.  The scratch belongs to the operator
+ * (allocated at the first call, freed by tpsrhs_destroy). */
+int tpsrhs_integrate(tpsrhs_handle h, int nrows, const double *field, const double *exact_q, int radial_weight,
+                     double *sum_out, double *sumsq_out);
+
+/* Per row of field (DEVICE [nrows][NDofs]): min_out, max_out and meanabs_out = sum_n |f_n| / NDofs (DEVICE [nrows], each
+ * may be NULL) -- computeMeanTimeDerivatives for field = y = Mult(x).  min and max start from +-inf and are kept with
+ * `<` / `>`: a NaN entry never wins (as in the wall distance); a NaN does propagate into meanabs.  Same summation
+ * structure, stream and refusals as tpsrhs_integrate. */
+int tpsrhs_nodal_stats(tpsrhs_handle h, int nrows, const double *field, double *min_out, double *max_out,
+                       double *meanabs_out);
+
+/* Monitor history inside the device time loop.  After every step of tpsrhs_advance / tpsrhs_advance_with a step counter
+ * goes up (tpsrhs_monitor_configure zeroes it); when count % interval == 0 one record is enqueued between the steps:
+ *   iters[record]              the count
+ *   times[record], dts[record] the time and the dt of the NEXT step, copied device-to-device from the loop's control block
+ *   totals[record][neq]        tpsrhs_integrate of the new x, radial_weight = the operator's axisymmetric flag
+ *   mins, maxs[record][neq]    tpsrhs_nodal_stats of x
+ * The semantics of the probes: nothing returns to the host, a record is never part of the captured step graph and never
+ * causes a re-capture; when `capacity` records are held further records are dropped and counted, and nothing is written
+ * past the end; tpsrhs_step and tpsrhs_rk4_step neither count nor record.  interval == 0 switches the monitor off and
+ * frees its buffers; a negative value, or capacity < 1 with the monitor on: TPSRHS_ERR_INVALID_ARGUMENT. */
+int tpsrhs_monitor_configure(tpsrhs_handle h, int64_t interval, int64_t capacity);
+/* Copies the held records to HOST arrays and synchronises the stream.  Any pointer may be NULL.  reset != 0 starts the
+ * buffer again (records and dropped count) and leaves the step counter alone.  Monitor not configured:
+ * TPSRHS_ERR_INVALID_ARGUMENT. */
+int tpsrhs_monitor_read(tpsrhs_handle h, int64_t *nrecords, int64_t *ndropped, int64_t *iters_out, double *times_out,
+                        double *dts_out, double *totals_out, double *mins_out, double *maxs_out, int reset);
+
 /* JouleHeating (src/forcing_terms.cpp:443-471): `joule_heating` is the DEVICE array of the
  * `joule_heating_` grid function (NDofs doubles, owned by the caller, read at every Mult; the EM solver
  * refreshes it between steps).  Positive entries are added to the total-energy equation and, for a

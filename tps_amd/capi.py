@@ -664,6 +664,11 @@ def load():
     lib.tpsrhs_probe_read.argtypes = [vp, _ip64, _ip64, vp, vp, vp, C.c_int]
     lib.tpsrhs_wall_faces.argtypes = [C.POINTER(Mesh), C.c_int, C.POINTER(BC), C.c_int, vp, C.c_int64, vp, _ip64]
     lib.tpsrhs_wall_distance.argtypes = [vp, C.c_int64, vp, vp]
+    lib.tpsrhs_quadrature_points.argtypes = [C.POINTER(Mesh), C.c_int, vp, vp, _ip64]
+    lib.tpsrhs_integrate.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp]
+    lib.tpsrhs_nodal_stats.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    lib.tpsrhs_monitor_configure.argtypes = [vp, C.c_int64, C.c_int64]
+    lib.tpsrhs_monitor_read.argtypes = [vp, _ip64, _ip64, vp, vp, vp, vp, vp, vp, C.c_int]
     lib.tpsrhs_set_dt.argtypes = [vp, C.c_double]
     lib.tpsrhs_set_forcing.argtypes = [vp, C.POINTER(Forcing)]
     lib.tpsrhs_set_joule_heating.argtypes = [vp, C.c_void_p]
@@ -690,6 +695,7 @@ EXPORTED_SYMBOLS = [
     "tpsrhs_locate_points", "tpsrhs_plane_points", "tpsrhs_sampler_create", "tpsrhs_sampler_destroy", "tpsrhs_sampler_info",
     "tpsrhs_sample", "tpsrhs_probe_configure", "tpsrhs_probe_read",
     "tpsrhs_wall_faces", "tpsrhs_wall_distance",
+    "tpsrhs_quadrature_points", "tpsrhs_integrate", "tpsrhs_nodal_stats", "tpsrhs_monitor_configure", "tpsrhs_monitor_read",
 ]
 
 

@@ -71,6 +71,7 @@ const char *kKernelNames[NKERN] = {"k_traces", "k_gradient", "k_flux"};
 
 struct tpsrhs_stats_state;  // statistics.hpp: running mean and velocity covariances (tpsrhs.hip only)
 struct tpsrhs_sampling_state;  // sampling.hpp: point samplers and probe records (tpsrhs.hip only)
+struct tpsrhs_integrals_state;  // integrals.hpp: reduction scratch and monitor records (tpsrhs.hip only)
 
 struct tpsrhs_operator {
   int dim = 0, order = 0, neq = 0, nvel = 0;
@@ -167,6 +168,9 @@ struct tpsrhs_operator {
   // tpsrhs_sampler_create / tpsrhs_probe_configure; NULL: none yet.  The host copy of the element vertices, the samplers
   // this operator owns and the probe buffer; owned by tpsrhs.hip like `stats`, and appended after it for the same reason.
   tpsrhs_sampling_state *sampling = nullptr;
+  // tpsrhs_integrate / tpsrhs_nodal_stats / tpsrhs_monitor_configure; NULL: none yet.  The reduction scratch and the monitor
+  // records; owned by tpsrhs.hip like `stats` and `sampling`, and appended after them for the same reason.
+  tpsrhs_integrals_state *integrals = nullptr;
 
   MeshDev mesh_dev() const {
     MeshDev m;

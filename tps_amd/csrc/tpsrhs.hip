@@ -4,6 +4,7 @@
 // HBM, and enqueues the three sweeps of kernels.hpp on one HIP stream per operator.  There is no
 // CPU fallback: without a HIP device tpsrhs_create returns TPSRHS_ERR_NO_DEVICE.
 #include "operator.hpp"
+#include "integrals.hpp"
 #include "physics_dryair.hpp"
 #include "physics_dryair_axisym.hpp"
 #include "physics_plasma.hpp"
@@ -674,13 +675,29 @@ inline bool probe_due_after_next(const tpsrhs_operator *h) {
   const tpsrhs_sampling_state *ss = h->sampling;
   return ss && ss->probe && (ss->count + 1) % ss->interval == 0;
 }
+// Monitor records (integrals.hpp): at the end of this file
+void integrals_release(tpsrhs_operator *h);
+void monitor_record(tpsrhs_operator *h, const double *x);
+inline void monitor_after_step(tpsrhs_operator *h, const double *x) {
+  tpsrhs_integrals_state *is = h->integrals;
+  if (!is || !is->interval) return;
+  is->count++;
+  if (is->count % is->interval == 0) monitor_record(h, x);
+}
+inline bool monitor_due_after_next(const tpsrhs_operator *h) {
+  const tpsrhs_integrals_state *is = h->integrals;
+  return is && is->interval && (is->count + 1) % is->interval == 0;
+}
 // What the time loop does between two steps, and whether any of it falls between the next two: everything that reads x
-// between steps goes through these two, so that the loop itself knows nothing about statistics or probes.
+// between steps goes through these two, so that the loop itself knows nothing about statistics, probes or the monitor.
 inline void after_step(tpsrhs_operator *h, const double *x) {
   stats_after_step(h, x);
   probe_after_step(h, x);
+  monitor_after_step(h, x);
 }
-inline bool work_due_after_next(const tpsrhs_operator *h) { return stats_due_after_next(h) || probe_due_after_next(h); }
+inline bool work_due_after_next(const tpsrhs_operator *h) {
+  return stats_due_after_next(h) || probe_due_after_next(h) || monitor_due_after_next(h);
+}
 
 }  // namespace
 
@@ -709,6 +726,7 @@ int tpsrhs_create(const tpsrhs_mesh *mesh, const tpsrhs_disc *disc, const tpsrhs
 int tpsrhs_destroy(tpsrhs_handle h) {
   if (h) stats_release(h);
   if (h) sampling_release(h);
+  if (h) integrals_release(h);
   delete h;
   return TPSRHS_OK;
 }
@@ -1896,6 +1914,241 @@ int tpsrhs_wall_distance(tpsrhs_handle h, int64_t num_faces, const double *face_
       launch_wall_distance<3>(h, num_faces, face_xyz, distance_out);
     else
       launch_wall_distance<2>(h, num_faces, face_xyz, distance_out);
+  });
+}
+
+}  // extern "C"
+
+// ---- volume integrals, nodal extrema and the monitor records (quadrature_points.hpp, integrals.hpp) -------------------------
+// After every other launch of this unit, as the integrators, the statistics, the sampling and the wall distance above.
+namespace {
+void monitor_off(tpsrhs_operator *h) {
+  tpsrhs_integrals_state *is = h->integrals;
+  if (!is) return;
+  if (is->d_times) {  // (allocated first: set whenever any of the five is)
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);  // a record may still be running
+    for (double *p : {is->d_times, is->d_dts, is->d_totals, is->d_mins, is->d_maxs})
+      if (p) (void)hipFree(p);
+  }
+  is->d_times = is->d_dts = is->d_totals = is->d_mins = is->d_maxs = nullptr;
+  is->interval = is->capacity = is->count = is->nrecords = is->ndropped = 0;
+  is->iters.clear();
+}
+
+void integrals_release(tpsrhs_operator *h) {
+  tpsrhs_integrals_state *is = h->integrals;
+  if (!is) return;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);  // a reduction may still be running
+  monitor_off(h);
+  if (is->d_partial) (void)hipFree(is->d_partial);
+  delete is;
+  h->integrals = nullptr;
+}
+
+// a grid of at most INTEG_MAXBLOCKS blocks over ne elements in batches of eb: -> (blocks, elements per block)
+void reduction_grid(int ne, int eb, int *blocks, int *run) {
+  const int batches = (ne + eb - 1) / eb;
+  const int per = std::max(1, (batches + INTEG_MAXBLOCKS - 1) / INTEG_MAXBLOCKS);
+  *run = per * eb;
+  *blocks = std::max(1, (batches + per - 1) / per);
+}
+
+template <int DIM, int P>
+int integ_segments() {
+  return IntegCfg<DIM, P>::EB;
+}
+
+// the state with its scratch, sized once: the grids depend on the mesh and the order only
+tpsrhs_integrals_state *integrals_of(tpsrhs_operator *h) {
+  if (h->integrals) return h->integrals;
+  int eb = 0;
+  switch (h->dim * 10 + h->order) {
+    case 21: eb = integ_segments<2, 1>(); break;
+    case 22: eb = integ_segments<2, 2>(); break;
+    case 23: eb = integ_segments<2, 3>(); break;
+    case 24: eb = integ_segments<2, 4>(); break;
+    case 25: eb = integ_segments<2, 5>(); break;
+    case 31: eb = integ_segments<3, 1>(); break;
+    case 32: eb = integ_segments<3, 2>(); break;
+    case 33: eb = integ_segments<3, 3>(); break;
+    case 34: eb = integ_segments<3, 4>(); break;
+    case 35: eb = integ_segments<3, 5>(); break;
+    default: throw Unsupported("tpsrhs_integrate: dim 2 or 3 and polynomial orders 1..5 are built");
+  }
+  std::unique_ptr<tpsrhs_integrals_state> is(new tpsrhs_integrals_state());
+  is->integ_eb = eb;
+  reduction_grid(h->ne, eb, &is->integ_blocks, &is->integ_run);
+  const int npe = static_cast<int>(h->ndofs / std::max(h->ne, 1));
+  is->stat_lpe = lanes_per_element(npe);
+  reduction_grid(h->ne, 64 / is->stat_lpe, &is->stat_blocks, &is->stat_run);
+  const int64_t per_row = std::max<int64_t>(2 * static_cast<int64_t>(is->integ_blocks) * eb,
+                                             3 * static_cast<int64_t>(is->stat_blocks) * (64 / is->stat_lpe));
+  is->d_partial = dev_alloc<double>(INTEG_ROWS * per_row);
+  h->integrals = is.release();
+  return h->integrals;
+}
+
+template <int DIM, int P>
+void launch_integrate(tpsrhs_operator *h, const tpsrhs_integrals_state *is, const QuadTab &tab, int nrows, const double *field,
+                      const double *exact, int radial, double *partial) {
+  typedef IntegCfg<DIM, P> C;
+  hipLaunchKernelGGL((k_integrate<DIM, P>), dim3(is->integ_blocks), dim3(64), 0, h->stream, h->ne, is->integ_run, nrows, h->ndofs,
+                     static_cast<int64_t>(h->ne) * C::NQD, radial, tab, h->d_verts, field, exact, partial);
+  HIP_CHECK(hipGetLastError());
+}
+
+// sum_out[nrows], sumsq_out[nrows] (either may be NULL) of field[nrows][NDofs] - exact[nrows][npts], on the operator's stream
+void integrate_field(tpsrhs_operator *h, int nrows, const double *field, const double *exact, int radial, double *sum_out,
+                     double *sumsq_out) {
+  tpsrhs_integrals_state *is = integrals_of(h);
+  if (h->ne == 0) {
+    if (sum_out) HIP_CHECK(hipMemsetAsync(sum_out, 0, sizeof(double) * nrows, h->stream));
+    if (sumsq_out) HIP_CHECK(hipMemsetAsync(sumsq_out, 0, sizeof(double) * nrows, h->stream));
+    return;
+  }
+  QuadTab tab = {};
+  const int n1 = h->order + 1, nq = quad_points_1d(h->order);
+  double nodes[TPSRHS_MAXORDER + 1], wts[TPSRHS_MAXORDER + 1];
+  segment_rule01(h->nc, n1, nodes, wts);  // the nodes of the operator's basis, as make_tables places them
+  gauss_legendre01(nq, tab.g, tab.w);
+  for (int q = 0; q < nq; q++)
+    for (int a = 0; a < n1; a++) tab.B[q * n1 + a] = lagrange(nodes, n1, a, tab.g[q]);
+  const int64_t npts = static_cast<int64_t>(h->ne) * (h->dim == 3 ? nq * nq * nq : nq * nq);
+  const int64_t np = static_cast<int64_t>(is->integ_blocks) * is->integ_eb;
+  for (int r0 = 0; r0 < nrows; r0 += INTEG_ROWS) {  // the stream orders the launches: one scratch serves every slab of rows
+    const int nr = std::min(INTEG_ROWS, nrows - r0);
+    const double *f = field + r0 * h->ndofs, *ex = exact ? exact + r0 * npts : nullptr;
+    switch (h->dim * 10 + h->order) {
+      case 21: launch_integrate<2, 1>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
+      case 22: launch_integrate<2, 2>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
+      case 23: launch_integrate<2, 3>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
+      case 24: launch_integrate<2, 4>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
+      case 25: launch_integrate<2, 5>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
+      case 31: launch_integrate<3, 1>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
+      case 32: launch_integrate<3, 2>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
+      case 33: launch_integrate<3, 3>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
+      case 34: launch_integrate<3, 4>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
+      case 35: launch_integrate<3, 5>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
+      default: throw Unsupported("tpsrhs_integrate: dim 2 or 3 and polynomial orders 1..5 are built");
+    }
+    hipLaunchKernelGGL(k_integrate_final<1024>, dim3(1), dim3(1024), 0, h->stream, nr, np, is->d_partial,
+                       sum_out ? sum_out + r0 : nullptr, sumsq_out ? sumsq_out + r0 : nullptr);
+    HIP_CHECK(hipGetLastError());
+  }
+}
+
+void nodal_stats_field(tpsrhs_operator *h, int nrows, const double *field, double *min_out, double *max_out, double *meanabs_out) {
+  tpsrhs_integrals_state *is = integrals_of(h);
+  const int npe = static_cast<int>(h->ndofs / std::max(h->ne, 1));
+  const int64_t np = static_cast<int64_t>(is->stat_blocks) * (64 / is->stat_lpe);
+  for (int r0 = 0; r0 < nrows; r0 += INTEG_ROWS) {
+    const int nr = std::min(INTEG_ROWS, nrows - r0);
+    // (ne == 0: one block without elements writes the empty partials +inf, -inf, 0)
+    hipLaunchKernelGGL(k_nodal_stats, dim3(is->stat_blocks, nr), dim3(64), 0, h->stream, h->ne, is->stat_run, npe, is->stat_lpe,
+                       h->ndofs, field + r0 * h->ndofs, is->d_partial);
+    HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_nodal_stats_final<1024>, dim3(1), dim3(1024), 0, h->stream, nr, np, h->ndofs, is->d_partial,
+                       min_out ? min_out + r0 : nullptr, max_out ? max_out + r0 : nullptr,
+                       meanabs_out ? meanabs_out + r0 : nullptr);
+    HIP_CHECK(hipGetLastError());
+  }
+}
+
+// One monitor record of the device vector x, stream-ordered, or one more dropped record when the buffer is full.
+void monitor_record(tpsrhs_operator *h, const double *x) {
+  tpsrhs_integrals_state *is = h->integrals;
+  if (is->nrecords >= is->capacity) {
+    is->ndropped++;
+    return;
+  }
+  const int64_t r = is->nrecords;
+  const int axisym = h->dim == 2 && h->nvel == 3;
+  integrate_field(h, h->neq, x, nullptr, axisym, is->d_totals + r * h->neq, nullptr);
+  nodal_stats_field(h, h->neq, x, is->d_mins + r * h->neq, is->d_maxs + r * h->neq, nullptr);
+  // {dt of the next step, time}: the loop's control block, which the variable-dt loop never has on the host
+  HIP_CHECK(hipMemcpyAsync(is->d_dts + r, h->d_ctl, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  HIP_CHECK(hipMemcpyAsync(is->d_times + r, h->d_ctl + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  is->iters.push_back(is->count);
+  is->nrecords++;
+}
+}  // namespace
+
+extern "C" {
+
+int tpsrhs_quadrature_points(const tpsrhs_mesh *mesh, int order, double *xyz_out, double *w_out, int64_t *npts_out) {
+  const int st = quadrature_points(mesh, order, xyz_out, w_out, npts_out);
+  if (st != TPSRHS_OK)
+    return fail(st, "tpsrhs_quadrature_points: needs a mesh of dim 2 or 3 with elem_coords, an order in 1..5 and npts_out");
+  return st;
+}
+
+int tpsrhs_integrate(tpsrhs_handle h, int nrows, const double *field, const double *exact_q, int radial_weight,
+                     double *sum_out, double *sumsq_out) {
+  if (!h || !field || nrows < 1)
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_integrate: needs a handle, nrows >= 1 and the device field");
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(h->device));
+    integrate_field(h, nrows, field, exact_q, radial_weight ? 1 : 0, sum_out, sumsq_out);
+  });
+}
+
+int tpsrhs_nodal_stats(tpsrhs_handle h, int nrows, const double *field, double *min_out, double *max_out, double *meanabs_out) {
+  if (!h || !field || nrows < 1)
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_nodal_stats: needs a handle, nrows >= 1 and the device field");
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(h->device));
+    nodal_stats_field(h, nrows, field, min_out, max_out, meanabs_out);
+  });
+}
+
+int tpsrhs_monitor_configure(tpsrhs_handle h, int64_t interval, int64_t capacity) {
+  if (!h) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_monitor_configure: NULL handle");
+  if (interval < 0 || capacity < 0)
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_monitor_configure: needs interval >= 0 (0: off) and capacity >= 0");
+  if (interval > 0 && capacity < 1) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_monitor_configure: needs capacity >= 1");
+  return guarded([&] {
+    monitor_off(h);
+    if (interval == 0) return;
+    HIP_CHECK(hipSetDevice(h->device));
+    tpsrhs_integrals_state *is = integrals_of(h);  // with the scratch: a record allocates nothing
+    is->d_times = dev_alloc<double>(capacity);  // (first: monitor_off frees the others when this one is set)
+    is->d_dts = dev_alloc<double>(capacity);
+    is->d_totals = dev_alloc<double>(capacity * h->neq);
+    is->d_mins = dev_alloc<double>(capacity * h->neq);
+    is->d_maxs = dev_alloc<double>(capacity * h->neq);
+    if (!h->d_ctl) h->d_ctl = dev_alloc<double>(3);  // the loop's {dt, time, max speed}: a record copies from there
+    is->interval = interval;
+    is->capacity = capacity;
+  });
+}
+
+int tpsrhs_monitor_read(tpsrhs_handle h, int64_t *nrecords, int64_t *ndropped, int64_t *iters_out, double *times_out,
+                        double *dts_out, double *totals_out, double *mins_out, double *maxs_out, int reset) {
+  if (!h) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_monitor_read: NULL handle");
+  tpsrhs_integrals_state *is = h->integrals;
+  if (!is || !is->interval)
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_monitor_read: the monitor is not configured (tpsrhs_monitor_configure)");
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(h->device));
+    const int64_t n = is->nrecords;
+    auto fetch = [&](double *dst, const double *src, int64_t count) {
+      if (dst && count) HIP_CHECK(hipMemcpyAsync(dst, src, sizeof(double) * count, hipMemcpyDeviceToHost, h->stream));
+    };
+    fetch(times_out, is->d_times, n);
+    fetch(dts_out, is->d_dts, n);
+    fetch(totals_out, is->d_totals, n * h->neq);
+    fetch(mins_out, is->d_mins, n * h->neq);
+    fetch(maxs_out, is->d_maxs, n * h->neq);
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (nrecords) *nrecords = n;
+    if (ndropped) *ndropped = is->ndropped;
+    if (iters_out && n) std::memcpy(iters_out, is->iters.data(), sizeof(int64_t) * n);
+    if (reset) {  // the buffer starts again; the step counter goes on
+      is->nrecords = is->ndropped = 0;
+      is->iters.clear();
+    }
   });
 }
 

@@ -361,6 +361,80 @@ class RHSoperator:
             raise TpsRhsError(st, "tpsrhs_wall_distance")
         return out
 
+    # -- volume integrals, extrema and the monitor history --------------------------------------------------------------------
+    def _rows(self, field: torch.Tensor) -> int:
+        n = self.NDofs
+        if field.dtype != torch.float64 or not field.is_cuda or not field.is_contiguous() or field.numel() % n or not field.numel():
+            raise ValueError("expected a contiguous float64 CUDA tensor of nrows * NDofs entries")
+        return field.numel() // n
+
+    def integrate(self, field: torch.Tensor, exact_q=None, radial=None):
+        """``(sum, sumsq)``, each a new CUDA tensor ``(nrows,)``: ``sum_q W_q g_q`` and ``sum_q W_q g_q^2`` of
+        ``g = field - exact_q`` on MFEM's default rule of ``GridFunction::ComputeLpError`` (Gauss-Legendre, order 2p + 3),
+        so that ``sumsq.sqrt()`` is the L2 error ``M2ulPhyS::checkSolutionError`` prints (``src/masa_handler.cpp:139-152``).
+        ``field``: ``nrows * NDofs`` entries (byNODES); ``exact_q``: ``(nrows, npts)`` at the points of
+        :func:`quadrature_points`, or ``None`` for 0; ``radial``: weight every point by its first coordinate (``None``:
+        the operator's axisymmetric flag).  Asynchronous on the operator's stream."""
+        nrows = self._rows(field)
+        if exact_q is not None:
+            if (exact_q.dtype != torch.float64 or not exact_q.is_cuda or not exact_q.is_contiguous()
+                    or exact_q.numel() != nrows * self.numQuadraturePoints()):
+                raise ValueError("expected exact_q as a contiguous float64 CUDA tensor of nrows * npts entries")
+        if radial is None:
+            radial = bool(self._disc.axisymmetric)
+        out = torch.empty((2, nrows), dtype=torch.float64, device=field.device)
+        st = self._lib.tpsrhs_integrate(self._h, nrows, C.c_void_p(field.data_ptr()),
+                                        C.c_void_p(exact_q.data_ptr()) if exact_q is not None else None, 1 if radial else 0,
+                                        C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_integrate")
+        return out[0], out[1]
+
+    def numQuadraturePoints(self) -> int:
+        return self._mesh.num_elements * (self._disc.order + 2) ** self.dim
+
+    def nodalStats(self, field: torch.Tensor):
+        """``(min, max, meanabs)`` of every row of ``field`` (``nrows * NDofs`` entries), new CUDA tensors ``(nrows,)``;
+        ``meanabs = sum |f| / NDofs`` is ``RHSoperator::computeMeanTimeDerivatives`` (``src/rhs_operator.cpp:833-849``)
+        for ``field = Mult(x)``.  A NaN entry never wins min / max and does poison meanabs."""
+        nrows = self._rows(field)
+        out = torch.empty((3, nrows), dtype=torch.float64, device=field.device)
+        st = self._lib.tpsrhs_nodal_stats(self._h, nrows, C.c_void_p(field.data_ptr()), C.c_void_p(out[0].data_ptr()),
+                                          C.c_void_p(out[1].data_ptr()), C.c_void_p(out[2].data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_nodal_stats")
+        return out[0], out[1], out[2]
+
+    def configureMonitor(self, interval: int, capacity: int):
+        """Monitor records inside :meth:`advance`: after every step a counter goes up (zeroed here), and when it is a
+        multiple of ``interval`` the count, the device-side time, the ``dt`` of the next step, the integrals of the
+        conserved state and its minima and maxima are appended to a device buffer of ``capacity`` records; further
+        records are dropped and counted.  ``interval=0`` switches the monitor off."""
+        st = self._lib.tpsrhs_monitor_configure(self._h, int(interval), int(capacity))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_monitor_configure")
+        self._monitor = int(capacity) if interval != 0 else None
+
+    def readMonitor(self, reset: bool = False):
+        """``dict(iters (nrec,), times, dts (nrec,), totals, mins, maxs (nrec, num_equation), ndropped)`` as numpy arrays;
+        synchronises.  ``reset`` starts the buffer again and leaves the step counter alone."""
+        capacity = getattr(self, "_monitor", None)
+        if capacity is None:
+            raise TpsRhsError(self._lib.tpsrhs_monitor_read(self._h, None, None, None, None, None, None, None, None, 0),
+                              "tpsrhs_monitor_read")
+        iters = np.zeros(capacity, dtype=np.int64)
+        times, dts = np.zeros(capacity), np.zeros(capacity)
+        totals, mins, maxs = (np.zeros((capacity, self.num_equation)) for _ in range(3))
+        nrec, ndrop = C.c_int64(0), C.c_int64(0)
+        st = self._lib.tpsrhs_monitor_read(self._h, C.byref(nrec), C.byref(ndrop), iters.ctypes.data, times.ctypes.data,
+                                           dts.ctypes.data, totals.ctypes.data, mins.ctypes.data, maxs.ctypes.data,
+                                           1 if reset else 0)
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_monitor_read")
+        n = nrec.value
+        return dict(iters=iters[:n].copy(), times=times[:n].copy(), dts=dts[:n].copy(), totals=totals[:n].copy(),
+                    mins=mins[:n].copy(), maxs=maxs[:n].copy(), ndropped=ndrop.value)
+
     def kernel_bytes(self):
         names = (C.c_char_p * 8)()
         b = (C.c_double * 8)()
@@ -470,6 +544,24 @@ def plane_points(point, normal, bb0, bb1, n: int) -> np.ndarray:
     if st != 0:
         raise TpsRhsError(st, "tpsrhs_plane_points")
     return out
+
+
+def quadrature_points(host_mesh, order: int):
+    """Host-only call of ``tpsrhs_quadrature_points``: ``(xyz (dim, npts), w (npts,))``, the points and weights (without
+    the radial factor) of the rule of :meth:`RHSoperator.integrate` -- tensor Gauss-Legendre with ``order + 2`` points per
+    direction, point ``q = e * NQ^dim + (i + j NQ + k NQ^2)``."""
+    lib = capi.load()
+    ma = capi.MeshArgs(host_mesh)
+    n = C.c_int64(0)
+    st = lib.tpsrhs_quadrature_points(C.byref(ma.c), int(order), None, None, C.byref(n))
+    if st != 0:
+        raise TpsRhsError(st, "tpsrhs_quadrature_points")
+    xyz = np.zeros((host_mesh.dim, n.value))
+    w = np.zeros(n.value)
+    st = lib.tpsrhs_quadrature_points(C.byref(ma.c), int(order), xyz.ctypes.data, w.ctypes.data, C.byref(n))
+    if st != 0:
+        raise TpsRhsError(st, "tpsrhs_quadrature_points")
+    return xyz, w
 
 
 def node_coordinates(host_mesh, order: int, basis_type: int = 0) -> np.ndarray:
