@@ -763,6 +763,35 @@ int tpsrhs_monitor_configure(tpsrhs_handle h, int64_t interval, int64_t capacity
 int tpsrhs_monitor_read(tpsrhs_handle h, int64_t *nrecords, int64_t *ndropped, int64_t *iters_out, double *times_out,
                         double *dts_out, double *totals_out, double *mins_out, double *maxs_out, int reset);
 
+/* ---- plasma post-processing fields: M2ulPhyS::updateVisualizationVariables (src/M2ulPhyS.cpp:4156-4263, the fields it
+ * registers at :1690-1787), which the reference has on the CPU only (its device build exits at :4157-4160) -------------
+ * One DEVICE array out[nrows][NDofs], the rows in the reference's registration order (names as it writes them):
+ *   X_<sp>, Y_<sp>, n_<sp>                       computeSpeciesPrimitives of the state, num_species rows each
+ *   viscosity, bulk_viscosity, thermal_cond_heavy, thermal_cond_elec      ComputeFluxTransportProperties
+ *   diff_vel_<sp>                                nvel rows per species, species-major (grid functions on nvelfes); the rows
+ *                                                past dim (the azimuthal one, axisymmetric) are zero, as the transport leaves them
+ *   electric_cond                                SrcTrns of ComputeSourceTransportProperties
+ *   momentum_tranfer_freq_<sp>                   SpeciesTrns (the spelling is the reference's); of one-temperature mixtures too
+ *   rxn_rate_1 .. rxn_rate_R                     progress rates kf (prod n^nu' - prod n^nu'' / kC), NOT species sources
+ * Point for point as the reference: the UNCLAMPED state, prim = Up and the gradients = gradUp of the state, Efield = 0, the
+ * rates from the number densities ComputeSourceTransportProperties returns, Chemistry's temperature floor inside the rate
+ * coefficients. */
+typedef struct tpsrhs_vis_layout { /* AuxiliaryVisualizationIndexes: first ROW of each group, -1 = absent */
+  int nrows;                        /* 4*nsp + nsp*nvel + 5 + num_reactions */
+  int Xsp, Ysp, nsp_, FluxTrns, diffVel, SrcTrns, SpeciesTrns, rxn; /* rxn = -1 without reactions */
+  int num_species, nvel, num_reactions;
+} tpsrhs_vis_layout;
+/* Host only, touches no device.  nvel = 3 when `axisymmetric` or dim == 3, else 2.  A NULL pointer, a dim other than
+ * 2 / 3 or an axisymmetric dim 3: TPSRHS_ERR_INVALID_ARGUMENT; dry air (the reference skips the whole block for it) and the
+ * table gas: TPSRHS_ERR_UNSUPPORTED. */
+int tpsrhs_visualization_layout(const tpsrhs_physics *physics, int dim, int axisymmetric, tpsrhs_vis_layout *out);
+/* visualization() of the reference (:4107-4112): refreshes the operator's Up and gradUp from x (tpsrhs_update_gradients,
+ * halo exchange included on a partitioned mesh), then fills out.  x, out: DEVICE, out[nrows][NDofs] of
+ * tpsrhs_visualization_layout for this operator; every row of every node is written.  Asynchronous on the operator's
+ * stream, like tpsrhs_get_plasma_conductivity.  TPSRHS_ERR_UNSUPPORTED, never a fallback: dry air, the table gas, and an
+ * operator with a mixing length set (the reference would route distance and radius through MixingLengthTransport). */
+int tpsrhs_visualization_fields(tpsrhs_handle h, const double *x, double *out);
+
 /* JouleHeating (src/forcing_terms.cpp:443-471): `joule_heating` is the DEVICE array of the
  * `joule_heating_` grid function (NDofs doubles, owned by the caller, read at every Mult; the EM solver
  * refreshes it between steps).  Positive entries are added to the total-energy equation and, for a

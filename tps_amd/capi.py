@@ -138,6 +138,12 @@ class Lte(C.Structure):  # LteMixtureInput + the TableInputs of src/M2ulPhyS.cpp
                 ("viscosity_table", Table), ("conductivity_table", Table), ("electric_conductivity_table", Table)]
 
 
+class VisLayout(C.Structure):  # tpsrhs_vis_layout: first ROW of each group of tpsrhs_visualization_fields, -1 = absent
+    _fields_ = [("nrows", C.c_int), ("Xsp", C.c_int), ("Ysp", C.c_int), ("nsp_", C.c_int), ("FluxTrns", C.c_int),
+                ("diffVel", C.c_int), ("SrcTrns", C.c_int), ("SpeciesTrns", C.c_int), ("rxn", C.c_int),
+                ("num_species", C.c_int), ("nvel", C.c_int), ("num_reactions", C.c_int)]
+
+
 class Physics(C.Structure):
     _fields_ = [("eq_system", C.c_int), ("working_fluid", C.c_int), ("dry_air", DryAir), ("mixture", PerfectMixture),
                 ("transport_model", C.c_int), ("constant_transport", ConstantTransport),
@@ -669,6 +675,8 @@ def load():
     lib.tpsrhs_nodal_stats.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     lib.tpsrhs_monitor_configure.argtypes = [vp, C.c_int64, C.c_int64]
     lib.tpsrhs_monitor_read.argtypes = [vp, _ip64, _ip64, vp, vp, vp, vp, vp, vp, C.c_int]
+    lib.tpsrhs_visualization_layout.argtypes = [C.POINTER(Physics), C.c_int, C.c_int, C.POINTER(VisLayout)]
+    lib.tpsrhs_visualization_fields.argtypes = [vp, vp, vp]
     lib.tpsrhs_set_dt.argtypes = [vp, C.c_double]
     lib.tpsrhs_set_forcing.argtypes = [vp, C.POINTER(Forcing)]
     lib.tpsrhs_set_joule_heating.argtypes = [vp, C.c_void_p]
@@ -696,7 +704,42 @@ EXPORTED_SYMBOLS = [
     "tpsrhs_sample", "tpsrhs_probe_configure", "tpsrhs_probe_read",
     "tpsrhs_wall_faces", "tpsrhs_wall_distance",
     "tpsrhs_quadrature_points", "tpsrhs_integrate", "tpsrhs_nodal_stats", "tpsrhs_monitor_configure", "tpsrhs_monitor_read",
+    "tpsrhs_visualization_layout", "tpsrhs_visualization_fields",
 ]
+
+
+FLUX_TRANS_NAMES = ("viscosity", "bulk_viscosity", "thermal_cond_heavy", "thermal_cond_elec")  # src/M2ulPhyS.cpp:1716-1737
+
+
+def visualization_layout(physics, dim, axisymmetric=False) -> VisLayout:
+    """Host-only call of ``tpsrhs_visualization_layout``: the rows of ``tpsrhs_visualization_fields``.  Raises
+    ``RuntimeError`` with the status in ``.status`` for a refused physics (dry air, the table gas)."""
+    lib = load()
+    out = VisLayout()
+    st = lib.tpsrhs_visualization_layout(C.byref(physics), int(dim), 1 if axisymmetric else 0, C.byref(out))
+    if st != 0:
+        e = RuntimeError(f"tpsrhs_visualization_layout: {lib.tpsrhs_status_string(st).decode()}: {lib.tpsrhs_last_error().decode()}")
+        e.status = st
+        raise e
+    return out
+
+
+def visualization_names(layout, species_names=None):
+    """``[(name, first row, number of rows)]`` in row order, with the reference's field names (``src/M2ulPhyS.cpp:1690-1787``;
+    ``momentum_tranfer_freq`` is its spelling).  ``species_names`` defaults to ``sp0 ..``."""
+    nsp = layout.num_species
+    sp = list(species_names) if species_names is not None else [f"sp{i}" for i in range(nsp)]
+    if len(sp) != nsp:
+        raise ValueError(f"{nsp} species names expected, got {len(sp)}")
+    out = []
+    for prefix, first in (("X_", layout.Xsp), ("Y_", layout.Ysp), ("n_", layout.nsp_)):
+        out += [(prefix + sp[i], first + i, 1) for i in range(nsp)]
+    out += [(name, layout.FluxTrns + i, 1) for i, name in enumerate(FLUX_TRANS_NAMES)]
+    out += [("diff_vel_" + sp[i], layout.diffVel + i * layout.nvel, layout.nvel) for i in range(nsp)]
+    out.append(("electric_cond", layout.SrcTrns, 1))
+    out += [("momentum_tranfer_freq_" + sp[i], layout.SpeciesTrns + i, 1) for i in range(nsp)]
+    out += [(f"rxn_rate_{r + 1}", layout.rxn + r, 1) for r in range(layout.num_reactions)]
+    return out
 
 
 def face_tables(host_mesh, bcs=()):

@@ -3314,4 +3314,6 @@ __global__ void k_pack(int nshared, int nfld, int n1, const int32_t *__restrict_
 }
 
 }  // namespace tpsrhs
+
+#include "visualization.hpp"  // k_vis_fields: after every other kernel, so that none of them moves
 #endif

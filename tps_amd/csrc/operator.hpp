@@ -171,6 +171,9 @@ struct tpsrhs_operator {
   // tpsrhs_integrate / tpsrhs_nodal_stats / tpsrhs_monitor_configure; NULL: none yet.  The reduction scratch and the monitor
   // records; owned by tpsrhs.hip like `stats` and `sampling`, and appended after them for the same reason.
   tpsrhs_integrals_state *integrals = nullptr;
+  // tpsrhs_visualization_fields: the post-processing passes of the plasma families (visualization.hpp); NULL for every other
+  // physics.  Appended after `integrals` for the same reason: the kernel families see the members above where they were.
+  void (*vis_fields)(tpsrhs_operator *, const VisRows &, const double *, double *) = nullptr;
 
   MeshDev mesh_dev() const {
     MeshDev m;
@@ -483,6 +486,25 @@ void pick_order(tpsrhs_operator *op) {
       throw Unsupported("polynomial order " + std::to_string(op->order) + " is not built for this physics (1.." +
                         std::to_string(PH::MAX_ORDER) + ")");
   }
+}
+
+// the four passes of tpsrhs_visualization_fields on the operator's stream: U = x, Up / gradUp the operator's own (just
+// refreshed by the caller), out [nrows][NDofs].  Instantiated in the units of plasma_vis_family.hpp only: a unit that does
+// not ask for it gets no kernel from it.
+template <class PH>
+void launch_vis_fields(tpsrhs_operator *op, const VisRows &rows, const double *x, double *out) {
+  const int64_t n = op->ndofs;
+  const int grid = static_cast<int>((n + 255) / 256);
+  if (grid == 0) return;
+  const typename PH::KArg prm_k = kernel_params<PH>(op);
+  hipLaunchKernelGGL((k_vis_fields<PH, VIS_SPECIES>), dim3(grid), dim3(256), 0, op->stream, prm_k, rows, n, x, op->d_Up, op->d_gradUp, out);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL((k_vis_fields<PH, VIS_FLUX>), dim3(grid), dim3(256), 0, op->stream, prm_k, rows, n, x, op->d_Up, op->d_gradUp, out);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL((k_vis_fields<PH, VIS_SIGMA>), dim3(grid), dim3(256), 0, op->stream, prm_k, rows, n, x, op->d_Up, op->d_gradUp, out);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL((k_vis_fields<PH, VIS_SOURCE>), dim3(grid), dim3(256), 0, op->stream, prm_k, rows, n, x, op->d_Up, op->d_gradUp, out);
+  HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace

@@ -874,6 +874,7 @@ struct PlasmaPhys {
   // src/transport_properties.cpp:392-449): the number densities of computeSpeciesPrimitives and the
   // electron momentum-transfer frequencies.  (The reference also evaluates the diffusion velocities and
   // the electric conductivity there; no term of the hot path reads them.)
+  // (The frequencies below exist a second time in source_props_full, for the post-processing fields: change both.)
   __device__ static inline void source_props(PRef p, const double *U, double Th, double Te, double *n,
                                              double *mtfreq) {
     const Species q = species(p, U);
@@ -1655,6 +1656,8 @@ struct PlasmaPhys {
   }
 
   // ---- SourceTerm::updateTerms at one node, src/source_term.cpp:107-251 ------------------------
+  // (The rate loop below exists a second time in progress_rates, for the post-processing fields: change both.
+  //  tests/test_gpu_visualization.py ties the two through the oracle: M sum_r (nu'' - nu') q_r against point_source.)
   __device__ static inline void source(PRef p, const double *Uin, const double *Upin, const double *g,
                                        double *src) {
     double U[NEQ], Up[NEQ];
@@ -1755,6 +1758,107 @@ struct PlasmaPhys {
         e *= 2.0 * me * ms / (ms + me) / (ms + me) * ne * t.mtfreq[sp];
         src[ITE] -= e;
       }
+    }
+  }
+
+  // ---- post-processing closures (visualization.hpp; M2ulPhyS::updateVisualizationVariables, src/M2ulPhyS.cpp:4233-4260) ----
+  // New functions beside source_props / source, which stay token for token: the sweeps inline those, and their device
+  // code is compared byte for byte (tools/device_asm_diff.py).
+  //
+  // ComputeSourceTransportProperties as the visualisation stores it, in two parts (two passes: the diffusivities behind the
+  // conductivity and the collision table behind the frequencies are never live together).
+  // SrcTrns::ELECTRIC_CONDUCTIVITY with the temperatures of Up (electric_conductivity above takes them from the state):
+  __device__ static inline double source_conductivity(PRef p, const double *U, double Th, double Te) {
+    TCoef c;
+    transport_coeffs(p, U, Th, Te, true, c);
+    double mho = 0.0;
+#pragma unroll
+    for (int sp = 0; sp < NSP; sp++) mho += c.mob[sp] * c.n[sp] * p.charge[sp];
+    return mho * kMolarQe;
+  }
+  // ... the number densities of computeSpeciesPrimitives and the electron momentum-transfer frequencies of EVERY mixture
+  // (source_props skips them for one temperature, where no term of the residual reads them):
+  __device__ static inline void source_props_full(PRef p, const double *U, double Th, double Te, double *n,
+                                                  double *mtfreq) {
+    const Species q = species(p, U);
+#pragma unroll
+    for (int sp = 0; sp < NSP; sp++) {
+      n[sp] = q.n[sp];
+      mtfreq[sp] = 0.0;
+    }
+    if (TRANSPORT == TRANSPORT_CONSTANT) {
+#pragma unroll
+      for (int sp = 0; sp < NSP; sp++) mtfreq[sp] = p.c_mtfreq[sp];
+    } else if (TRANSPORT == TRANSPORT_ARGON_MIXTURE) {  // src/gas_transport.cpp:1445-1459
+      const double mff = 4. / 3. * kAvogadro * sqrt(8. * kBoltz / kPi);
+      const MixColl c = mix_inputs(p, q.n, Th, Te);
+      const double vth = (mff / (15. / 4. * kBoltz * 5. / 16. * sqrt(kPi * kBoltz))) * p.ke_fac * fast_sqrt(Te);  // mff sqrt(T_e / m_e)
+      const CollTab pe = coll_table<1, 1>(p.cmask_e, true, c);
+#pragma unroll
+      for (int sp = 0; sp < NSP; sp++) {
+        if (sp == IE) continue;
+        mtfreq[sp] = vth * q.n[sp] * coll_pick(p, sp, IE, pe);
+        if (p.multiply) mtfreq[sp] *= p.mult_spcs;
+      }
+    } else {  // src/gas_transport.cpp:700-722
+      const double mff = 4. / 3. * kAvogadro * sqrt(8. * kBoltz / kPi);
+      const Debye d = debye(q.n, Th, Te, fast_rcp(Th), fast_rcp(Te));
+      const double QeAr = coll::eAr1r(1, flog(Te)), Qatt = coll::att11(d.e) * d.circle;
+      const double vth = (mff / (15. / 4. * kBoltz * 5. / 16. * sqrt(kPi * kBoltz))) * p.ke_fac * fast_sqrt(Te);  // mff sqrt(T_e / m_e)
+      mtfreq[I_ION] = vth * q.n[I_ION] * Qatt;
+      mtfreq[I_N] = vth * q.n[I_N] * QeAr;
+      if (p.multiply) {
+#pragma unroll
+        for (int sp = 0; sp < NSP; sp++) mtfreq[sp] *= p.mult_spcs;
+      }
+    }
+  }
+  // Chemistry::computeForwardRateCoeffs / computeEquilibriumConstants / computeProgressRate (src/chemistry.cpp:161-299):
+  // q_r = kf (prod n^nu' - prod n^nu'' / kC) of every reaction, handed to `store(r, q_r)` one at a time (an array indexed
+  // by the run-time r would live in scratch memory).  The rate loop of `source` above, without the species sources.
+  template <class F>
+  __device__ static inline void progress_rates(PRef p, const double *n, double Th, double Te, F &&store) {
+    const ChemDev &c = *p.chem;
+    const double Thl = fmax(Th, c.min_temperature), Tel = fmax(Te, c.min_temperature);
+    int tab_root = -1, tab_idx = 0;  // the last table interval found: (grid, temperature) -> interval
+    double tab_temp = 0.0;
+    for (int r = 0; r < c.num_reactions; r++) {
+      const bool el = (c.electron_index < 0) ? false : (c.reactant[c.electron_index + r * NSP] != 0);
+      const double temp = el ? Tel : Thl;
+      const double A = c.rate[0 + r * 3], b = c.rate[1 + r * 3], E = c.rate[2 + r * 3];
+      double kf;
+      if (c.model[r] == TPSRHS_ARRHENIUS) {
+        kf = A * fexp(b * flog(temp) - E / kRgas / temp);
+      } else if (c.model[r] == TPSRHS_HOFFERTLIEN) {
+        const double tf = E / kBoltz / temp;
+        kf = A * (tf + 2.0) * fexp(b * flog(temp) - tf);
+      } else {
+        const TableDev &tb = c.table[r];
+        const int root = c.table_share[r];
+        int ti;
+        if (root == tab_root && temp == tab_temp) {
+          ti = tab_idx;
+        } else {
+          ti = table_interval(tb, temp);
+          tab_root = root;
+          tab_temp = temp;
+          tab_idx = ti;
+        }
+        const double xt = tb.x_log ? flog(temp) : temp;
+        kf = tb.a[ti] + tb.b[ti] * xt;
+        if (tb.f_log) kf = fexp(kf);
+      }
+      double rate = 1.0;
+#pragma unroll
+      for (int sp = 0; sp < NSP; sp++) rate *= ipow(n[sp], c.reactant[sp + r * NSP]);
+      if (c.detailed_balance[r]) {
+        const double kc = c.keq[0 + r * 3] * fexp(c.keq[1 + r * 3] * flog(temp) - c.keq[2 + r * 3] / temp);
+        double bwd = 1.0;
+#pragma unroll
+        for (int sp = 0; sp < NSP; sp++) bwd *= ipow(n[sp], c.product[sp + r * NSP]);
+        rate -= bwd / kc;
+      }
+      store(r, kf * rate);
     }
   }
 };

@@ -1,0 +1,3 @@
+// Post-processing passes of the plasma kernel family: dim 2, 2 velocity components, 8 species, ambipolar = true.
+#include "plasma_vis_family.hpp"
+TPSRHS_PLASMA_VIS_FAMILY(pick_plasma_vis_2d_n8a, 2, 2, 8, true)

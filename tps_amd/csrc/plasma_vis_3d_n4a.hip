@@ -1,0 +1,3 @@
+// Post-processing passes of the plasma kernel family: dim 3, 3 velocity components, 4 species, ambipolar = true.
+#include "plasma_vis_family.hpp"
+TPSRHS_PLASMA_VIS_FAMILY(pick_plasma_vis_3d_n4a, 3, 3, 4, true)

@@ -1,0 +1,3 @@
+// Post-processing passes of the plasma kernel family: dim 3, 3 velocity components, 6 species, ambipolar = false.
+#include "plasma_vis_family.hpp"
+TPSRHS_PLASMA_VIS_FAMILY(pick_plasma_vis_3d_n6, 3, 3, 6, false)

@@ -1,0 +1,3 @@
+// Post-processing passes of the plasma kernel family: dim 2, 3 velocity components, 6 species, ambipolar = true.
+#include "plasma_vis_family.hpp"
+TPSRHS_PLASMA_VIS_FAMILY(pick_plasma_vis_axi_n6a, 2, 3, 6, true)

@@ -1,0 +1,3 @@
+// Post-processing passes of the plasma kernel family: dim 2, 3 velocity components, 7 species, ambipolar = true.
+#include "plasma_vis_family.hpp"
+TPSRHS_PLASMA_VIS_FAMILY(pick_plasma_vis_axi_n7a, 2, 3, 7, true)

@@ -2153,3 +2153,74 @@ int tpsrhs_monitor_read(tpsrhs_handle h, int64_t *nrecords, int64_t *ndropped, i
 }
 
 }  // extern "C"
+
+// =============================================================================================
+// Plasma post-processing fields (visualization.hpp): M2ulPhyS::updateVisualizationVariables on the device.  No kernel of
+// this unit: the passes live in shared objects of their own (plasma_vis_family.hpp), loaded at the first call and reached
+// through tpsrhs_operator::vis_fields.
+// =============================================================================================
+namespace {
+int vis_layout(const tpsrhs_physics &ph, int dim, int axisymmetric, tpsrhs_vis_layout *out) {
+  if (ph.working_fluid == TPSRHS_DRY_AIR)
+    throw Unsupported("visualization fields: dry air has none (the reference skips the block, src/M2ulPhyS.cpp:4199)");
+  if (ph.working_fluid != TPSRHS_USER_DEFINED)
+    throw Unsupported("visualization fields: built for the species mixtures (fluid = user_defined), not for the table gas");
+  const int nsp = ph.mixture.num_species, R = ph.chemistry.num_reactions;
+  if (nsp < 1 || nsp > TPSRHS_MAXSPECIES) throw std::invalid_argument("tpsrhs_visualization_layout: num_species");
+  if (R < 0 || R > TPSRHS_MAXREACTIONS) throw std::invalid_argument("tpsrhs_visualization_layout: num_reactions");
+  const int nvel = (axisymmetric || dim == 3) ? 3 : 2;
+  tpsrhs_vis_layout l;
+  l.num_species = nsp;
+  l.nvel = nvel;
+  l.num_reactions = R;
+  int row = 0;  // the registration order of src/M2ulPhyS.cpp:1690-1787
+  l.Xsp = row, row += nsp;
+  l.Ysp = row, row += nsp;
+  l.nsp_ = row, row += nsp;
+  l.FluxTrns = row, row += 4;         // FluxTrns::NUM_FLUX_TRANS
+  l.diffVel = row, row += nsp * nvel;
+  l.SrcTrns = row, row += 1;          // SrcTrns::NUM_SRC_TRANS
+  l.SpeciesTrns = row, row += nsp;    // SpeciesTrns::NUM_SPECIES_COEFFS = 1
+  l.rxn = R > 0 ? row : -1, row += R;
+  l.nrows = row;
+  *out = l;
+  return row;
+}
+}  // namespace
+
+extern "C" {
+
+int tpsrhs_visualization_layout(const tpsrhs_physics *physics, int dim, int axisymmetric, tpsrhs_vis_layout *out) {
+  if (!physics || !out) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_visualization_layout: NULL argument");
+  if ((dim != 2 && dim != 3) || (dim == 3 && axisymmetric))
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_visualization_layout: dim 2 (planar or axisymmetric) or 3");
+  return guarded([&] { vis_layout(*physics, dim, axisymmetric, out); });
+}
+
+int tpsrhs_visualization_fields(tpsrhs_handle h, const double *x, double *out) {
+  if (!h || !x || !out) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_visualization_fields: NULL argument");
+  return guarded([&] {
+    tpsrhs_vis_layout l;
+    vis_layout(h->phys, h->dim, h->nvel > h->dim ? 1 : 0, &l);  // refuses dry air and the table gas
+    if (h->mixlen.distance)
+      throw Unsupported("visualization fields: a mixing length is set; the reference would evaluate MixingLengthTransport "
+                        "with the wall distance and the radius here, which is not built");
+    if (!h->vis_fields) {  // the passes of this family: a shared object of its own, loaded at the first call
+      const tpsrhs_perfect_mixture &mx = h->phys.mixture;
+      const int tr = (h->phys.transport_model == TPSRHS_CONSTANT)
+                         ? TRANSPORT_CONSTANT
+                         : (h->phys.transport_model == TPSRHS_ARGON_MINIMAL ? TRANSPORT_ARGON_MINIMAL : TRANSPORT_ARGON_MIXTURE);
+      const char *geo = (h->dim == 3) ? "3d" : (h->nvel > h->dim ? "axi" : "2d");
+      const std::string unit = std::string("plasma_vis_") + geo + "_n" + std::to_string(mx.num_species) + (mx.ambipolar ? "a" : "");
+      char msg[512] = {0};
+      const int rc = load_family(unit)(h, mx.two_temperature ? 1 : 0, tr, msg, static_cast<int>(sizeof msg));
+      if (rc != TPSRHS_OK || !h->vis_fields) throw Unsupported(std::string("visualization fields: ") + msg);
+    }
+    HIP_CHECK(hipSetDevice(h->device));
+    h->launch(h, x, nullptr, true);  // rhsOperator->updateGradients(*U, false): Up and gradUp of x
+    const VisRows rows = {l.Xsp, l.Ysp, l.nsp_, l.FluxTrns, l.diffVel, l.SrcTrns, l.SpeciesTrns, l.rxn};
+    h->vis_fields(h, rows, x, out);
+  });
+}
+
+}  // extern "C"

@@ -125,6 +125,26 @@ class RHSoperator:
             raise TpsRhsError(st, "tpsrhs_get_plasma_conductivity")
         return out
 
+    def visualizationLayout(self) -> "capi.VisLayout":
+        """Rows of :meth:`visualizationFields` for this operator's physics (``tpsrhs_visualization_layout``, host only)."""
+        return capi.visualization_layout(self._physics, self.dim, bool(self._disc.axisymmetric))
+
+    def visualizationFields(self, x: torch.Tensor, species_names=None, return_array: bool = False):
+        """The derived fields of ``M2ulPhyS::updateVisualizationVariables`` (``src/M2ulPhyS.cpp:4156-4263``) at the nodes of
+        the state ``x``: an ordered dict from the reference's field name to a view of ONE ``[nrows, NDofs]`` device tensor
+        (``[NDofs]`` per scalar field, ``[nvel, NDofs]`` for ``diff_vel_<sp>``).  ``Up`` and ``gradUp`` of the operator are
+        refreshed from ``x`` first.  Asynchronous on the operator's stream.  ``return_array``: ``(dict, the whole tensor)``
+        -- any rows of it go through :meth:`integrate`, :meth:`nodalStats` and :meth:`PointSampler.sample` as they are."""
+        self._check(x)
+        lay = self.visualizationLayout()
+        names = capi.visualization_names(lay, species_names)
+        out = torch.empty((lay.nrows, self.NDofs), dtype=torch.float64, device=self.device)
+        st = self._lib.tpsrhs_visualization_fields(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_visualization_fields")
+        fields = {name: (out[first] if rows == 1 else out[first:first + rows]) for name, first, rows in names}
+        return (fields, out) if return_array else fields
+
     # -- measurement helpers -----------------------------------------------------------------
     def enable_kernel_timing(self, on=True):
         self._lib.tpsrhs_enable_kernel_timing(self._h, 1 if on else 0)
