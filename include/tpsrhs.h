@@ -558,6 +558,47 @@ int tpsrhs_sampler_info(tpsrhs_sampler_handle s, int64_t *npts, int64_t *nfound,
  * nrows < 1: TPSRHS_ERR_INVALID_ARGUMENT before any device work. */
 int tpsrhs_sample(tpsrhs_sampler_handle s, int nrows, const double *field, double *out);
 
+/* ---- point location on the device, and a field carried from one mesh to another ------------------------------------------
+ * utils/pfield_interpolate.cpp:36-155 (a restart on another mesh or order) and CycleAvgJouleCoupling
+ * (src/cycle_avg_joule_coupling.cpp:159-363, flow mesh <-> EM mesh at every coupling iteration) both form the physical
+ * coordinates of the target's nodes, FindPointsGSLIB::Interpolate the source field there and SetFromTrueDofs the result.
+ * Here the location rule is the one above, run with one lane per point (k_locate): the same bins, the same ascending walk,
+ * the same Newton iteration and acceptance, from the same source text as the host locator.  The device contracts a*b + c
+ * into an FMA where the host build does not, so reference coordinates differ from the host's in the last bits, and the
+ * accepted element can differ ONLY for a point whose reference coordinate lies within rounding of -tol or 1 + tol -- a
+ * point 1e-10 outside an element, not a point on a face. */
+
+/* tpsrhs_sampler_create with the points already on the device and nothing returning to the host:
+ * xyz DEVICE [dim][npts].  The points keep the caller's order (no sort: identity permutation) --
+ * meant for point sets that are spatially coherent already, such as the nodes of another mesh.  The search grid of the
+ * operator's mesh is uploaded once per (operator, tol) and freed by tpsrhs_destroy.  tpsrhs_sampler_info copies elem and
+ * ref from the device on demand; tpsrhs_sample and the probes take such a sampler as any other.  Asynchronous on the
+ * operator's stream (xyz must stay valid until that work has run); a NULL handle or output, npts < 0, NULL points with
+ * npts > 0 or a NaN tol: TPSRHS_ERR_INVALID_ARGUMENT before any device work. */
+int tpsrhs_sampler_create_device(tpsrhs_handle h, int64_t npts, const double *xyz, double tol, double fill,
+                                 tpsrhs_sampler_handle *out);
+
+/* Physical coordinates of the operator's DG nodes, DEVICE out[dim][NDofs], from the order-1 vertex map at
+ * the operator's 1-D nodes (what pfield_interpolate.cpp:114-135 builds with ElementTransformation::Transform).
+ * Asynchronous on the operator's stream.  A NULL argument: TPSRHS_ERR_INVALID_ARGUMENT. */
+int tpsrhs_node_coordinates(tpsrhs_handle h, double *xyz_out);
+
+/* pfield_interpolate.cpp:138-146 / CycleAvgJouleCoupling: field_dst[row][NDofs_dst] = field_src at the nodes of dst.
+ * nrows rows of a byNODES field of src (x, primitives, means, visualization fields, a conductivity ...), DEVICE arrays.
+ * Nodes of dst outside the mesh of src get `fill` in every row; *num_missing (may be NULL) is their count.
+ * The first call for a pair creates a device sampler on src at dst's node coordinates and keeps it on src, keyed by dst
+ * and tol (fill is taken at every call); it is dropped when either operator is destroyed.  Later calls are one k_sample
+ * launch.  The work runs on src's stream and dst's stream waits for it through an event: no host synchronisation unless
+ * num_missing is asked for (the locating first call of a pair synchronises once, to free the coordinates).  Orders, bases and element counts may differ freely; axisymmetric runs are plain 2-D in
+ * (r, z); on partitioned meshes each rank transfers from its own elements (the sampler contract above).
+ * NULL handle or array, nrows < 1, NaN tol, operators of different dim: TPSRHS_ERR_INVALID_ARGUMENT; operators on
+ * different devices: TPSRHS_ERR_UNSUPPORTED -- both before any device work. */
+int tpsrhs_transfer(tpsrhs_handle src, tpsrhs_handle dst, int nrows, const double *field_src, double *field_dst,
+                    double tol, double fill, int64_t *num_missing);
+/* Diagnostics of the pair cache: how many tpsrhs_transfer calls on src created a sampler (ran k_locate) and how many found
+ * theirs.  Either output may be NULL. */
+int tpsrhs_transfer_stats(tpsrhs_handle src, int64_t *num_located, int64_t *num_cache_hits);
+
 /* Probe time histories inside the device time loop (the per-iteration use of the interpolator: the reference calls its
  * plane dump from solveStep, src/M2ulPhyS.cpp:2052-2096, on the host).  After
  * every step of tpsrhs_advance / tpsrhs_advance_with a step counter goes up (tpsrhs_probe_configure zeroes it); when

@@ -37,6 +37,7 @@ ADIAB, ISOTH, SHTH, NONE_THMCND = 0, 1, 2, 3  # ThermalCondition of viscous_gene
 FORWARD_EULER, RK2, RK3_SSP, RK4, RK6 = 1, 2, 3, 4, 6
 INTEGRATORS = {"forwardEuler": FORWARD_EULER, "rk2": RK2, "rk3": RK3_SSP, "rk4": RK4, "rk6": RK6}
 ERR_INVALID_ARGUMENT, ERR_UNSUPPORTED = 1, 2
+ERR_NO_DEVICE = 5
 
 
 def integrator_value(integrator):
@@ -666,6 +667,10 @@ def load():
     lib.tpsrhs_sampler_destroy.argtypes = [vp]
     lib.tpsrhs_sampler_info.argtypes = [vp, _ip64, _ip64, vp, vp]
     lib.tpsrhs_sample.argtypes = [vp, C.c_int, vp, vp]
+    lib.tpsrhs_sampler_create_device.argtypes = [vp, C.c_int64, vp, C.c_double, C.c_double, C.POINTER(vp)]
+    lib.tpsrhs_node_coordinates.argtypes = [vp, vp]
+    lib.tpsrhs_transfer.argtypes = [vp, vp, C.c_int, vp, vp, C.c_double, C.c_double, _ip64]
+    lib.tpsrhs_transfer_stats.argtypes = [vp, _ip64, _ip64]
     lib.tpsrhs_probe_configure.argtypes = [vp, vp, C.c_int64, C.c_int64]
     lib.tpsrhs_probe_read.argtypes = [vp, _ip64, _ip64, vp, vp, vp, C.c_int]
     lib.tpsrhs_wall_faces.argtypes = [C.POINTER(Mesh), C.c_int, C.POINTER(BC), C.c_int, vp, C.c_int64, vp, _ip64]
@@ -702,6 +707,7 @@ EXPORTED_SYMBOLS = [
     "tpsrhs_stats_num_variances",
     "tpsrhs_locate_points", "tpsrhs_plane_points", "tpsrhs_sampler_create", "tpsrhs_sampler_destroy", "tpsrhs_sampler_info",
     "tpsrhs_sample", "tpsrhs_probe_configure", "tpsrhs_probe_read",
+    "tpsrhs_sampler_create_device", "tpsrhs_node_coordinates", "tpsrhs_transfer", "tpsrhs_transfer_stats",
     "tpsrhs_wall_faces", "tpsrhs_wall_distance",
     "tpsrhs_quadrature_points", "tpsrhs_integrate", "tpsrhs_nodal_stats", "tpsrhs_monitor_configure", "tpsrhs_monitor_read",
     "tpsrhs_visualization_layout", "tpsrhs_visualization_fields",

@@ -12,6 +12,10 @@
 // those whose box does not hold it, inverts the map of the others by Newton from the element centre, and takes the FIRST
 // whose reference coordinates all lie in [-tol, 1 + tol]: on a face between two elements, where a DG field has two
 // values, the element with the lower index answers.  That choice is part of the contract (include/tpsrhs.h).
+//
+// Two parts: build_locate_grid makes the search structure (host only), locate_one is the rule for ONE point, and it, with
+// what it calls, is marked TPSRHS_HD -- __host__ __device__ when hipcc compiles tpsrhs.hip, nothing for a plain C++ compiler --
+// so that the device locator (locate_device.hpp: k_locate) runs this very text.
 #ifndef TPSRHS_POINT_LOCATE_HPP_
 #define TPSRHS_POINT_LOCATE_HPP_
 
@@ -32,6 +36,13 @@
 #define TPSRHS_IEEE_DIVISION
 #endif
 
+// The per-point half (locate_one and what it calls) runs on the host and, in tpsrhs.hip, on the device (locate_device.hpp)
+#if defined(__HIPCC__)
+#define TPSRHS_HD __host__ __device__
+#else
+#define TPSRHS_HD
+#endif
+
 namespace tpsrhs {
 
 constexpr double LOCATE_DEFAULT_TOL = 1e-10;
@@ -45,7 +56,7 @@ inline int mfem_to_lex_corner(int v) {
 
 // x(xi) of one element (v: [2^dim][dim], lexicographic corners) and, when J is non-NULL, J[a * dim + d] = dx_a / dxi_d
 template <int DIM>
-inline void vertex_map(const double *v, const double *xi, double *x, double *J) {
+TPSRHS_HD inline void vertex_map(const double *v, const double *xi, double *x, double *J) {
   constexpr int NV = 1 << DIM;
   for (int a = 0; a < DIM; a++) x[a] = 0.0;
   if (J)
@@ -69,7 +80,7 @@ inline void vertex_map(const double *v, const double *xi, double *x, double *J) 
 
 // s = J^{-1} r by Cramer's rule; false when J is singular to working precision
 template <int DIM>
-inline bool solve_small(const double *J, const double *r, double *s) {
+TPSRHS_HD inline bool solve_small(const double *J, const double *r, double *s) {
   TPSRHS_IEEE_DIVISION
   if (DIM == 2) {
     const double det = J[0] * J[3] - J[1] * J[2];
@@ -90,7 +101,7 @@ inline bool solve_small(const double *J, const double *r, double *s) {
 // Newton on x(xi) = p from the element centre.  true: converged (the last correction is below 1e-13, so by quadratic
 // convergence the remaining error is rounding); the reference coordinates are NOT clamped.
 template <int DIM>
-inline bool invert_vertex_map(const double *v, const double *p, double *xi) {
+TPSRHS_HD inline bool invert_vertex_map(const double *v, const double *p, double *xi) {
   for (int d = 0; d < DIM; d++) xi[d] = 0.5;
   for (int it = 0; it < LOCATE_MAX_NEWTON; it++) {
     double x[DIM], J[DIM * DIM], r[DIM], s[DIM];
@@ -108,20 +119,67 @@ inline bool invert_vertex_map(const double *v, const double *p, double *xi) {
   return false;
 }
 
-// verts: [ne][2^dim][dim] with lexicographic corners.  The layouts of xyz, elem_out, ref_out: tpsrhs_locate_points.
+// The search structure of one mesh and one tolerance (the element boxes are inflated by it): what FindPointsGSLIB::Setup
+// leaves behind.  Built on the host; the device locator (locate_device.hpp) reads an uploaded copy through the same view.
+struct LocateGrid {
+  int dim = 0, nb = 1;                                            // nb bins in every direction
+  double glo[3] = {0.0, 0.0, 0.0}, ghi[3] = {0.0, 0.0, 0.0};      // bounding box of the inflated element boxes
+  double inv_h[3] = {0.0, 0.0, 0.0};                              // bins per unit length
+  std::vector<double> lo, hi;                                     // [ne][dim] inflated element boxes
+  std::vector<int64_t> start;                                     // [nb^dim + 1] CSR offsets into list
+  std::vector<int32_t> list;                                      // the elements of every bin, ascending in e
+};
+
+// Raw pointers into a LocateGrid, host or device: what locate_one reads.  Passed by value (a kernel argument on the device).
 template <int DIM>
-inline void locate_points_lex(int ne, const double *verts, int64_t npts, const double *xyz, double tol, int32_t *elem_out,
-                              double *ref_out) {
-  constexpr int NV = 1 << DIM;
-  for (int64_t i = 0; i < npts; i++) {
-    elem_out[i] = -1;
-    for (int d = 0; d < DIM; d++) ref_out[i + d * npts] = 0.0;
+struct LocateGridView {
+  double glo[DIM], ghi[DIM], inv_h[DIM];
+  int nb;
+  const double *lo, *hi;
+  const int64_t *start;
+  const int32_t *list;
+};
+
+template <int DIM>
+inline LocateGridView<DIM> locate_grid_view(const LocateGrid &g, const double *lo, const double *hi, const int64_t *start,
+                                            const int32_t *list) {
+  LocateGridView<DIM> v;
+  for (int d = 0; d < DIM; d++) {
+    v.glo[d] = g.glo[d];
+    v.ghi[d] = g.ghi[d];
+    v.inv_h[d] = g.inv_h[d];
   }
-  if (ne <= 0 || npts <= 0) return;
+  v.nb = g.nb;
+  v.lo = lo;
+  v.hi = hi;
+  v.start = start;
+  v.list = list;
+  return v;
+}
+template <int DIM>
+inline LocateGridView<DIM> locate_grid_view(const LocateGrid &g) {
+  return locate_grid_view<DIM>(g, g.lo.data(), g.hi.data(), g.start.data(), g.list.data());
+}
+
+// monotone in x: a point inside an element's box falls in a bin the element lists
+TPSRHS_HD inline int locate_bin_of(double glo, double inv_h, int nb, double x) {
+  const double t = (x - glo) * inv_h;
+  if (!(t > 0.0)) return 0;
+  return t >= nb ? nb - 1 : static_cast<int>(t);
+}
+
+// verts: [ne][2^dim][dim] with lexicographic corners, ne >= 1.
+template <int DIM>
+inline LocateGrid build_locate_grid(int ne, const double *verts, double tol) {
+  constexpr int NV = 1 << DIM;
+  LocateGrid g;
+  g.dim = DIM;
   // element boxes.  A point with reference coordinates in [-tol, 1 + tol] lies within tol * (sum of the edge extents) of the
   // vertex hull, which is at most DIM * tol * (box size) per direction: the boxes are inflated by that much.
-  std::vector<double> lo(static_cast<size_t>(ne) * DIM), hi(static_cast<size_t>(ne) * DIM);
-  double glo[DIM], ghi[DIM];
+  std::vector<double> &lo = g.lo, &hi = g.hi;
+  lo.resize(static_cast<size_t>(ne) * DIM);
+  hi.resize(static_cast<size_t>(ne) * DIM);
+  double *glo = g.glo, *ghi = g.ghi;
   for (int e = 0; e < ne; e++) {
     const double *v = verts + static_cast<size_t>(e) * NV * DIM;
     for (int d = 0; d < DIM; d++) {
@@ -140,18 +198,14 @@ inline void locate_points_lex(int ne, const double *verts, int64_t npts, const d
   // bins: about one element per bin, the same count in every direction
   int nb = static_cast<int>(std::floor(std::pow(static_cast<double>(ne), 1.0 / DIM) + 0.5));
   nb = std::max(1, std::min(nb, DIM == 2 ? 2048 : 160));
-  double inv_h[DIM];
+  g.nb = nb;
+  double *inv_h = g.inv_h;
   for (int d = 0; d < DIM; d++) inv_h[d] = ghi[d] > glo[d] ? nb / (ghi[d] - glo[d]) : 0.0;
-  auto bin_of = [&](int d, double x) {  // monotone in x: a point inside an element's box falls in a bin the element lists
-    const double t = (x - glo[d]) * inv_h[d];
-    if (!(t > 0.0)) return 0;
-    return t >= nb ? nb - 1 : static_cast<int>(t);
-  };
   auto for_bins = [&](int e, auto &&f) {
     int b0[3] = {0, 0, 0}, b1[3] = {0, 0, 0};
     for (int d = 0; d < DIM; d++) {
-      b0[d] = bin_of(d, lo[static_cast<size_t>(e) * DIM + d]);
-      b1[d] = bin_of(d, hi[static_cast<size_t>(e) * DIM + d]);
+      b0[d] = locate_bin_of(glo[d], inv_h[d], nb, lo[static_cast<size_t>(e) * DIM + d]);
+      b1[d] = locate_bin_of(glo[d], inv_h[d], nb, hi[static_cast<size_t>(e) * DIM + d]);
     }
     for (int k = b0[2]; k <= b1[2]; k++)
       for (int j = b0[1]; j <= b1[1]; j++)
@@ -159,39 +213,65 @@ inline void locate_points_lex(int ne, const double *verts, int64_t npts, const d
   };
   size_t nbins = 1;
   for (int d = 0; d < DIM; d++) nbins *= nb;
-  std::vector<int64_t> start(nbins + 1, 0);
+  std::vector<int64_t> &start = g.start;
+  start.assign(nbins + 1, 0);
   for (int e = 0; e < ne; e++) for_bins(e, [&](size_t b) { start[b + 1]++; });
   for (size_t b = 0; b < nbins; b++) start[b + 1] += start[b];
-  std::vector<int32_t> list(static_cast<size_t>(start[nbins]));
+  g.list.resize(static_cast<size_t>(start[nbins]));
   {
     std::vector<int64_t> fill(start.begin(), start.end() - 1);
-    for (int e = 0; e < ne; e++) for_bins(e, [&](size_t b) { list[static_cast<size_t>(fill[b]++)] = e; });  // ascending in e
+    for (int e = 0; e < ne; e++) for_bins(e, [&](size_t b) { g.list[static_cast<size_t>(fill[b]++)] = e; });  // ascending in e
   }
+  return g;
+}
+
+// One point p[DIM]: the element that holds it (-1: none; xi_out is then 0) and its reference coordinates.  Host and device
+// run this text; the device contracts a * b + c into an FMA, so its reference coordinates differ from the host's in the
+// last bits, and the accepted element can differ only for a point whose coordinate lies within rounding of -tol or
+// 1 + tol -- 1e-10 outside an element, not on a face.
+template <int DIM>
+TPSRHS_HD inline int32_t locate_one(const LocateGridView<DIM> &g, const double *verts, const double *p, double tol,
+                                    double *xi_out) {
+  constexpr int NV = 1 << DIM;
+  for (int d = 0; d < DIM; d++) xi_out[d] = 0.0;
+  bool inside = true;
+  for (int d = 0; d < DIM; d++) inside = inside && p[d] >= g.glo[d] && p[d] <= g.ghi[d];  // false for a NaN
+  if (!inside) return -1;
+  size_t b = 0;
+  for (int d = DIM - 1; d >= 0; d--) b = b * g.nb + locate_bin_of(g.glo[d], g.inv_h[d], g.nb, p[d]);
+  for (int64_t q = g.start[b]; q < g.start[b + 1]; q++) {
+    const int32_t e = g.list[static_cast<size_t>(q)];
+    bool in_box = true;
+    for (int d = 0; d < DIM; d++)
+      in_box = in_box && p[d] >= g.lo[static_cast<size_t>(e) * DIM + d] && p[d] <= g.hi[static_cast<size_t>(e) * DIM + d];
+    if (!in_box) continue;
+    double xi[DIM];
+    if (!invert_vertex_map<DIM>(verts + static_cast<size_t>(e) * NV * DIM, p, xi)) continue;
+    bool accept = true;
+    for (int d = 0; d < DIM; d++) accept = accept && xi[d] >= -tol && xi[d] <= 1.0 + tol;
+    if (!accept) continue;
+    for (int d = 0; d < DIM; d++) xi_out[d] = xi[d];
+    return e;
+  }
+  return -1;
+}
+
+// verts: [ne][2^dim][dim] with lexicographic corners.  The layouts of xyz, elem_out, ref_out: tpsrhs_locate_points.
+template <int DIM>
+inline void locate_points_lex(int ne, const double *verts, int64_t npts, const double *xyz, double tol, int32_t *elem_out,
+                              double *ref_out) {
   for (int64_t i = 0; i < npts; i++) {
-    double p[DIM];
-    bool inside = true;
-    for (int d = 0; d < DIM; d++) {
-      p[d] = xyz[i + d * npts];
-      inside = inside && p[d] >= glo[d] && p[d] <= ghi[d];  // false for a NaN
-    }
-    if (!inside) continue;
-    size_t b = 0;
-    for (int d = DIM - 1; d >= 0; d--) b = b * nb + bin_of(d, p[d]);
-    for (int64_t q = start[b]; q < start[b + 1]; q++) {
-      const int e = list[static_cast<size_t>(q)];
-      bool in_box = true;
-      for (int d = 0; d < DIM; d++)
-        in_box = in_box && p[d] >= lo[static_cast<size_t>(e) * DIM + d] && p[d] <= hi[static_cast<size_t>(e) * DIM + d];
-      if (!in_box) continue;
-      double xi[DIM];
-      if (!invert_vertex_map<DIM>(verts + static_cast<size_t>(e) * NV * DIM, p, xi)) continue;
-      bool accept = true;
-      for (int d = 0; d < DIM; d++) accept = accept && xi[d] >= -tol && xi[d] <= 1.0 + tol;
-      if (!accept) continue;
-      elem_out[i] = e;
-      for (int d = 0; d < DIM; d++) ref_out[i + d * npts] = xi[d];
-      break;
-    }
+    elem_out[i] = -1;
+    for (int d = 0; d < DIM; d++) ref_out[i + d * npts] = 0.0;
+  }
+  if (ne <= 0 || npts <= 0) return;
+  const LocateGrid grid = build_locate_grid<DIM>(ne, verts, tol);
+  const LocateGridView<DIM> g = locate_grid_view<DIM>(grid);
+  for (int64_t i = 0; i < npts; i++) {
+    double p[DIM], xi[DIM];
+    for (int d = 0; d < DIM; d++) p[d] = xyz[i + d * npts];
+    elem_out[i] = locate_one<DIM>(g, verts, p, tol, xi);
+    for (int d = 0; d < DIM; d++) ref_out[i + d * npts] = xi[d];
   }
 }
 

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/tpsrhs.h"
+#include "point_locate.hpp"
 
 struct tpsrhs_operator;
 
@@ -30,6 +31,26 @@ struct tpsrhs_sampler {
   int32_t *d_elem = nullptr;  // [npts]
   double *d_ref = nullptr;    // [dim][npts]
   int64_t *d_perm = nullptr;  // [npts] sorted position -> the caller's index
+  // tpsrhs_sampler_create_device: located by k_locate (locate_device.hpp), in the caller's order (d_perm is the identity);
+  // nfound, elem and ref above are copied from the device the first time they are asked for
+  bool on_device = false, host_valid = true;
+  unsigned long long *d_nfound = nullptr;
+};
+
+// one uploaded search grid (point_locate.hpp: LocateGrid) of the operator's mesh; the element boxes depend on the tolerance
+struct tpsrhs_locate_grid_dev {
+  double tol = 0.0;
+  tpsrhs::LocateGrid host;  // the scalars; its vectors are emptied after the upload
+  double *d_lo = nullptr, *d_hi = nullptr;
+  int64_t *d_start = nullptr;
+  int32_t *d_list = nullptr;
+};
+
+// tpsrhs_transfer: the sampler on this operator (the source) at the nodes of `dst`
+struct tpsrhs_transfer_entry {
+  tpsrhs_operator *dst = nullptr;
+  double tol = 0.0;
+  tpsrhs_sampler *sampler = nullptr;
 };
 
 // behind tpsrhs_operator::sampling; owned by tpsrhs.hip
@@ -43,6 +64,11 @@ struct tpsrhs_sampling_state {
   std::vector<int64_t> iters;        // [nrecords] `count` at each record: the host issues every step and knows it
   double *d_values = nullptr;        // [capacity][neq][npts]
   double *d_times = nullptr;         // [capacity], copied from d_ctl[1] on the stream
+  // device location (tpsrhs_sampler_create_device): one grid per tolerance, uploaded at first use
+  std::vector<tpsrhs_locate_grid_dev *> grids;
+  // tpsrhs_transfer with this operator as the source: one sampler per (dst, tol), and how often it was made / found
+  std::vector<tpsrhs_transfer_entry> transfers;
+  int64_t num_located = 0, num_cache_hits = 0;
 };
 
 namespace tpsrhs {

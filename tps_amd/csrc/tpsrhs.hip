@@ -5,6 +5,7 @@
 // CPU fallback: without a HIP device tpsrhs_create returns TPSRHS_ERR_NO_DEVICE.
 #include "operator.hpp"
 #include "integrals.hpp"
+#include "locate_device.hpp"
 #include "physics_dryair.hpp"
 #include "physics_dryair_axisym.hpp"
 #include "physics_plasma.hpp"
@@ -663,6 +664,7 @@ inline bool stats_due_after_next(const tpsrhs_operator *h) {
 }
 // Probe records (sampling.hpp): at the end of this file
 void sampling_release(tpsrhs_operator *h);
+void transfer_release(tpsrhs_operator *h);
 void probe_record(tpsrhs_operator *h, const double *x);
 // the same two questions for the probes: count the step and enqueue a record when one is due / is one due after the next step?
 inline void probe_after_step(tpsrhs_operator *h, const double *x) {
@@ -725,6 +727,7 @@ int tpsrhs_create(const tpsrhs_mesh *mesh, const tpsrhs_disc *disc, const tpsrhs
 
 int tpsrhs_destroy(tpsrhs_handle h) {
   if (h) stats_release(h);
+  if (h) transfer_release(h);
   if (h) sampling_release(h);
   if (h) integrals_release(h);
   delete h;
@@ -1624,7 +1627,16 @@ void sampler_free(tpsrhs_sampler *s) {
   if (s->d_elem) (void)hipFree(s->d_elem);
   if (s->d_ref) (void)hipFree(s->d_ref);
   if (s->d_perm) (void)hipFree(s->d_perm);
+  if (s->d_nfound) (void)hipFree(s->d_nfound);
   delete s;
+}
+
+void locate_grid_free(tpsrhs_locate_grid_dev *g) {
+  if (g->d_lo) (void)hipFree(g->d_lo);
+  if (g->d_hi) (void)hipFree(g->d_hi);
+  if (g->d_start) (void)hipFree(g->d_start);
+  if (g->d_list) (void)hipFree(g->d_list);
+  delete g;
 }
 
 void probe_off(tpsrhs_operator *h) {
@@ -1649,8 +1661,31 @@ void sampling_release(tpsrhs_operator *h) {
   (void)hipStreamSynchronize(h->stream);  // a sample may still be running
   probe_off(h);
   for (tpsrhs_sampler *s : ss->samplers) sampler_free(s);
+  for (tpsrhs_locate_grid_dev *g : ss->grids) locate_grid_free(g);
   delete ss;
   h->sampling = nullptr;
+}
+
+// The sources of tpsrhs_transfer that hold a cached sampler: the destruction of ANY operator looks here for samplers at
+// its nodes (the cache is keyed by the address of dst, which the next tpsrhs_create may hand out again).
+std::mutex g_transfer_mu;
+std::vector<tpsrhs_operator *> g_transfer_sources;
+
+void sampler_remove(tpsrhs_operator *h, tpsrhs_sampler *s);
+
+// h is being destroyed: forget it as a source (sampling_release frees its samplers) and drop every sampler at its nodes
+void transfer_release(tpsrhs_operator *h) {
+  std::lock_guard<std::mutex> lock(g_transfer_mu);
+  auto &src = g_transfer_sources;
+  src.erase(std::remove(src.begin(), src.end(), h), src.end());
+  for (tpsrhs_operator *o : src) {
+    auto &tr = o->sampling->transfers;  // exists: o holds a cached sampler
+    for (size_t k = tr.size(); k-- > 0;)
+      if (tr[k].dst == h) {
+        sampler_remove(o, tr[k].sampler);
+        tr.erase(tr.begin() + static_cast<std::ptrdiff_t>(k));
+      }
+  }
 }
 
 template <int DIM, int P>
@@ -1698,6 +1733,134 @@ void probe_record(tpsrhs_operator *h, const double *x) {
   HIP_CHECK(hipMemcpyAsync(ss->d_times + r, h->d_ctl + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
   ss->iters.push_back(ss->count);
   ss->nrecords++;
+}
+
+// s, a live sampler of h, leaves it
+void sampler_remove(tpsrhs_operator *h, tpsrhs_sampler *s) {
+  tpsrhs_sampling_state *ss = h->sampling;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);  // a sample may still be running
+  if (ss->probe == s) probe_off(h);
+  ss->samplers.erase(std::find(ss->samplers.begin(), ss->samplers.end(), s));
+  sampler_free(s);
+}
+
+// The host copies of a device-located sampler (elem, ref, nfound), fetched once; synchronises the stream.
+void sampler_fetch(tpsrhs_sampler *s) {
+  if (s->host_valid) return;
+  tpsrhs_operator *h = s->owner;
+  HIP_CHECK(hipSetDevice(h->device));
+  unsigned long long nf = 0;
+  s->elem.resize(static_cast<size_t>(s->npts));
+  s->ref.resize(static_cast<size_t>(s->npts) * h->dim);
+  HIP_CHECK(hipMemcpyAsync(&nf, s->d_nfound, sizeof(nf), hipMemcpyDeviceToHost, h->stream));
+  if (s->npts) {
+    HIP_CHECK(hipMemcpyAsync(s->elem.data(), s->d_elem, s->elem.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipMemcpyAsync(s->ref.data(), s->d_ref, s->ref.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+  s->nfound = static_cast<int64_t>(nf);
+  s->host_valid = true;
+}
+// ... and the count alone (tpsrhs_transfer's num_missing): 8 bytes instead of the arrays
+int64_t sampler_nfound(tpsrhs_sampler *s) {
+  if (s->host_valid) return s->nfound;
+  tpsrhs_operator *h = s->owner;
+  unsigned long long nf = 0;
+  HIP_CHECK(hipMemcpyAsync(&nf, s->d_nfound, sizeof(nf), hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+  return static_cast<int64_t>(nf);
+}
+
+// The search grid of h's mesh for this tolerance on the device, built and uploaded at first use.
+template <int DIM>
+LocateGridView<DIM> device_grid(tpsrhs_operator *h, double tol) {
+  if (!h->sampling) h->sampling = new tpsrhs_sampling_state();
+  tpsrhs_sampling_state *ss = h->sampling;
+  tpsrhs_locate_grid_dev *g = nullptr;
+  for (tpsrhs_locate_grid_dev *c : ss->grids)
+    if (c->tol == tol) g = c;
+  if (!g) {
+    std::unique_ptr<tpsrhs_locate_grid_dev> up(new tpsrhs_locate_grid_dev());
+    up->tol = tol;
+    up->host = build_locate_grid<DIM>(h->ne, h->topo.verts.data(), tol);
+    struct Guard {
+      tpsrhs_locate_grid_dev *g;
+      ~Guard() {
+        if (g) locate_grid_free(g);
+      }
+    } guard{up.release()};
+    g = guard.g;
+    g->d_lo = dev_upload(g->host.lo);
+    g->d_hi = dev_upload(g->host.hi);
+    g->d_start = dev_upload(g->host.start);
+    g->d_list = dev_upload(g->host.list);
+    for (auto *v : {&g->host.lo, &g->host.hi}) std::vector<double>().swap(*v);
+    std::vector<int64_t>().swap(g->host.start);
+    std::vector<int32_t>().swap(g->host.list);
+    ss->grids.push_back(g);
+    guard.g = nullptr;
+  }
+  return locate_grid_view<DIM>(g->host, g->d_lo, g->d_hi, g->d_start, g->d_list);
+}
+
+template <int DIM>
+void launch_locate(tpsrhs_operator *h, tpsrhs_sampler *s, const double *xyz, double tol) {
+  constexpr int BLOCK = 64;
+  const int64_t grid = (s->npts + BLOCK - 1) / BLOCK;
+  if (grid >= (int64_t(1) << 31)) throw Unsupported("tpsrhs_sampler_create_device: more than 2^37 points");
+  const LocateGridView<DIM> g = device_grid<DIM>(h, tol);
+  HIP_CHECK(hipMemsetAsync(s->d_nfound, 0, sizeof(unsigned long long), h->stream));
+  if (grid == 0) return;
+  hipLaunchKernelGGL((k_locate<DIM, BLOCK>), dim3(static_cast<unsigned>(grid)), dim3(BLOCK), 0, h->stream, g, h->d_verts, s->npts,
+                     xyz, tol, s->d_elem, s->d_ref, s->d_perm, s->d_nfound);
+  HIP_CHECK(hipGetLastError());
+}
+
+// a sampler of h at the DEVICE points xyz[dim][npts], located on h's stream; registered with h
+tpsrhs_sampler *sampler_create_device(tpsrhs_operator *h, int64_t npts, const double *xyz, double tol, double fill) {
+  if (h->ne <= 0) throw Unsupported("tpsrhs_sampler_create_device: the operator has no elements");
+  const double t = tol > 0.0 ? tol : LOCATE_DEFAULT_TOL;
+  tpsrhs_sampler *s = new tpsrhs_sampler();
+  struct Guard {
+    tpsrhs_sampler *s;
+    ~Guard() {
+      if (s) sampler_free(s);
+    }
+  } guard{s};
+  s->owner = h;
+  s->npts = npts;
+  s->fill = fill;
+  s->on_device = true;
+  s->host_valid = false;
+  s->d_elem = dev_alloc<int32_t>(npts);
+  s->d_ref = dev_alloc<double>(npts * h->dim);
+  s->d_perm = dev_alloc<int64_t>(npts);
+  s->d_nfound = dev_alloc<unsigned long long>(1);
+  if (h->dim == 2)
+    launch_locate<2>(h, s, xyz, t);
+  else
+    launch_locate<3>(h, s, xyz, t);
+  h->sampling->samplers.push_back(s);  // exists: device_grid made it
+  guard.s = nullptr;
+  return s;
+}
+
+void node_coordinates_device(tpsrhs_operator *h, double *xyz_out, hipStream_t stream) {
+  SampleNodes nodes = {};
+  double wts[TPSRHS_MAXORDER + 1];
+  segment_rule01(h->nc, h->order + 1, nodes.x, wts);  // as sample_field
+  constexpr int BLOCK = 256;
+  const int64_t grid = (h->ndofs + BLOCK - 1) / BLOCK;
+  if (grid == 0) return;
+  if (grid >= (int64_t(1) << 31)) throw Unsupported("tpsrhs_node_coordinates: more than 2^39 nodes");
+  if (h->dim == 2)
+    hipLaunchKernelGGL((k_node_coordinates<2, BLOCK>), dim3(static_cast<unsigned>(grid)), dim3(BLOCK), 0, stream, h->ndofs,
+                       h->order + 1, nodes, h->d_verts, xyz_out);
+  else
+    hipLaunchKernelGGL((k_node_coordinates<3, BLOCK>), dim3(static_cast<unsigned>(grid)), dim3(BLOCK), 0, stream, h->ndofs,
+                       h->order + 1, nodes, h->d_verts, xyz_out);
+  HIP_CHECK(hipGetLastError());
 }
 
 // is s a live sampler?  (its owner is then s->owner)
@@ -1782,17 +1945,16 @@ int tpsrhs_sampler_destroy(tpsrhs_sampler_handle s) {
   if (!s) return TPSRHS_OK;
   tpsrhs_operator *h = s->owner;
   if (!sampler_alive(s, h)) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_sampler_destroy: not a sampler of a live operator");
-  tpsrhs_sampling_state *ss = h->sampling;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);  // a sample may still be running
-  if (ss->probe == s) probe_off(h);
-  ss->samplers.erase(std::find(ss->samplers.begin(), ss->samplers.end(), s));
-  sampler_free(s);
+  sampler_remove(h, s);
   return TPSRHS_OK;
 }
 
 int tpsrhs_sampler_info(tpsrhs_sampler_handle s, int64_t *npts, int64_t *nfound, int32_t *elem_out, double *ref_out) {
   if (!s) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_sampler_info: NULL sampler");
+  if (!s->host_valid) {  // located on the device: the host copies come on demand
+    const int st = guarded([&] { sampler_fetch(s); });
+    if (st != TPSRHS_OK) return st;
+  }
   if (npts) *npts = s->npts;
   if (nfound) *nfound = s->nfound;
   if (elem_out && s->npts) std::memcpy(elem_out, s->elem.data(), s->elem.size() * sizeof(int32_t));
@@ -1808,6 +1970,82 @@ int tpsrhs_sample(tpsrhs_sampler_handle s, int nrows, const double *field, doubl
     HIP_CHECK(hipSetDevice(h->device));
     sample_field(h, s, nrows, field, out);
   });
+}
+
+int tpsrhs_sampler_create_device(tpsrhs_handle h, int64_t npts, const double *xyz, double tol, double fill,
+                                 tpsrhs_sampler_handle *out) {
+  if (out) *out = nullptr;
+  if (!h || !out || npts < 0 || (npts > 0 && !xyz) || std::isnan(tol))
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_sampler_create_device: needs a handle, npts >= 0, the device points and a tolerance that is a number");
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(h->device));
+    *out = sampler_create_device(h, npts, xyz, tol, fill);
+  });
+}
+
+int tpsrhs_node_coordinates(tpsrhs_handle h, double *xyz_out) {
+  if (!h || !xyz_out) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_node_coordinates: NULL argument");
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(h->device));
+    node_coordinates_device(h, xyz_out, h->stream);
+  });
+}
+
+int tpsrhs_transfer(tpsrhs_handle src, tpsrhs_handle dst, int nrows, const double *field_src, double *field_dst, double tol,
+                    double fill, int64_t *num_missing) {
+  if (!src || !dst || !field_src || !field_dst || nrows < 1 || std::isnan(tol))
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_transfer: needs two operators, nrows >= 1, non-NULL device arrays and a tolerance that is a number");
+  if (src->dim != dst->dim)
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_transfer: the operators differ in dim");
+  if (src->device != dst->device)
+    return fail(TPSRHS_ERR_UNSUPPORTED, "tpsrhs_transfer: the operators are on different devices");
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(src->device));
+    const double t = tol > 0.0 ? tol : LOCATE_DEFAULT_TOL;
+    tpsrhs_sampler *s = nullptr;
+    {
+      std::lock_guard<std::mutex> lock(g_transfer_mu);
+      if (src->sampling)
+        for (const tpsrhs_transfer_entry &e : src->sampling->transfers)
+          if (e.dst == dst && e.tol == t) s = e.sampler;
+      if (s) {
+        src->sampling->num_cache_hits++;
+      } else {
+        // the nodes of dst, on src's stream (they depend on nothing dst's stream writes), live until they are located
+        double *xyz = dev_alloc<double>(static_cast<size_t>(dst->ndofs) * dst->dim);
+        struct Guard {
+          double *p;
+          ~Guard() { (void)hipFree(p); }
+        } guard{xyz};
+        node_coordinates_device(dst, xyz, src->stream);
+        s = sampler_create_device(src, dst->ndofs, xyz, t, fill);
+        HIP_CHECK(hipStreamSynchronize(src->stream));  // once per pair: xyz is freed below
+        src->sampling->transfers.push_back({dst, t, s});
+        src->sampling->num_located++;
+        if (std::find(g_transfer_sources.begin(), g_transfer_sources.end(), src) == g_transfer_sources.end())
+          g_transfer_sources.push_back(src);
+      }
+    }
+    s->fill = fill;
+    sample_field(src, s, nrows, field_src, field_dst);
+    if (dst->stream != src->stream) {  // dst's stream reads field_dst after this
+      hipEvent_t ev;
+      HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      hipError_t e1 = hipEventRecord(ev, src->stream);
+      hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(dst->stream, ev, 0) : e1;
+      (void)hipEventDestroy(ev);  // released when the record has completed
+      HIP_CHECK(e2);
+    }
+    if (num_missing) *num_missing = s->npts - sampler_nfound(s);
+  });
+}
+
+int tpsrhs_transfer_stats(tpsrhs_handle src, int64_t *num_located, int64_t *num_cache_hits) {
+  if (!src) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_transfer_stats: NULL handle");
+  const tpsrhs_sampling_state *ss = src->sampling;
+  if (num_located) *num_located = ss ? ss->num_located : 0;
+  if (num_cache_hits) *num_cache_hits = ss ? ss->num_cache_hits : 0;
+  return TPSRHS_OK;
 }
 
 int tpsrhs_probe_configure(tpsrhs_handle h, tpsrhs_sampler_handle s, int64_t interval, int64_t capacity) {

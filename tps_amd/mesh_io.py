@@ -10,7 +10,9 @@ reference checkout: none is available to test against).
 
 Boundary elements of a periodic mesh: MFEM keeps the faces of the periodic planes in the ``boundary`` section; a face that
 two elements share is an INTERIOR face for the DG operators (``Mesh::GetBdrFaceTransformations`` returns NULL there, so the
-reference's boundary integrators skip it): they are dropped here."""
+reference's boundary integrators skip it): they are dropped here.
+
+:func:`write_mfem_mesh` writes the same format for non-periodic meshes (tools/transfer_restart.py and its tests)."""
 import numpy as np
 
 from .meshgen import HostMesh
@@ -114,6 +116,31 @@ def read_mfem_mesh(path) -> HostMesh:
     keep = np.array(keep, dtype=np.int64)
     return HostMesh(dim, nvert, np.ascontiguousarray(ev), np.ascontiguousarray(coords),
                     np.ascontiguousarray(bv[keep]).reshape(len(keep), nv_el // 2), np.ascontiguousarray(battr[keep]))
+
+
+def write_mfem_mesh(path, mesh: HostMesh):
+    """The inverse of :func:`read_mfem_mesh` for a mesh whose vertex ids carry the geometry (no periodic identification:
+    every occurrence of a vertex id has the same coordinates; anything else raises): ``MFEM mesh v1.0`` with plain
+    ``vertices``, element attribute 1, coordinates with 17 significant digits, so that reading the file gives back the
+    same doubles."""
+    dim, ne = mesh.dim, mesh.num_elements
+    ev, ex = np.asarray(mesh.elem_vertices), np.asarray(mesh.elem_coords)
+    xyz = np.zeros((mesh.num_vertices, dim))
+    xyz[ev.ravel()] = ex.reshape(-1, dim)
+    if not np.array_equal(xyz[ev], ex):
+        raise ValueError("write_mfem_mesh: a vertex id occurs with two positions (a periodic mesh needs a nodes grid function)")
+    bv, ba = np.asarray(mesh.bdr_vertices), np.asarray(mesh.bdr_attributes)
+    geom, bgeom = (_SQUARE, 1) if dim == 2 else (_CUBE, _SQUARE)
+    with open(path, "w") as fh:
+        fh.write(f"MFEM mesh v1.0\n\ndimension\n{dim}\n\nelements\n{ne}\n")
+        for e in range(ne):
+            fh.write(f"1 {geom} " + " ".join(str(int(v)) for v in ev[e]) + "\n")
+        fh.write(f"\nboundary\n{bv.shape[0]}\n")
+        for b in range(bv.shape[0]):
+            fh.write(f"{int(ba[b])} {bgeom} " + " ".join(str(int(v)) for v in bv[b]) + "\n")
+        fh.write(f"\nvertices\n{mesh.num_vertices}\n{dim}\n")
+        for v in range(mesh.num_vertices):
+            fh.write(" ".join(f"{c:.17g}" for c in xyz[v]) + "\n")
 
 
 def refine_uniform(mesh: HostMesh, levels: int = 1) -> HostMesh:

@@ -286,10 +286,49 @@ class RHSoperator:
     def createSampler(self, xyz, tol: float = 0.0, fill: float = 0.0) -> "PointSampler":
         """``FindPointsGSLIB::Setup`` + ``FindPoints`` on this operator's mesh (``src/gslib_interpolator.cpp:53-67``):
         ``xyz`` is a host array ``(dim, npts)``; ``tol <= 0`` is 1e-10; ``fill`` is the value of points outside the mesh.
+        A float64 CUDA tensor ``(dim, npts)`` takes the device route instead (``tpsrhs_sampler_create_device``): the points
+        are located by a kernel, keep their order and never visit the host -- meant for point sets that are spatially
+        coherent already, such as :meth:`nodeCoordinates` of another operator.
         The operator owns the sampler: closing the operator closes it."""
         s = PointSampler(self, xyz, tol, fill)
         self._samplers = [w for w in getattr(self, "_samplers", []) if w() is not None] + [weakref.ref(s)]
         return s
+
+    def nodeCoordinates(self) -> torch.Tensor:
+        """Physical coordinates of the DG nodes, a new CUDA tensor ``(dim, NDofs)`` (``tpsrhs_node_coordinates``): what
+        ``utils/pfield_interpolate.cpp:114-135`` forms with ``ElementTransformation::Transform``; the device counterpart
+        of :func:`node_coordinates`.  Asynchronous on the operator's stream."""
+        out = torch.empty((self.dim, self.NDofs), dtype=torch.float64, device=self.device)
+        st = self._lib.tpsrhs_node_coordinates(self._h, C.c_void_p(out.data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_node_coordinates")
+        return out
+
+    def transferFrom(self, src_op: "RHSoperator", field: torch.Tensor, tol: float = 0.0, fill: float = 0.0):
+        """``field`` of ``src_op`` at the nodes of this operator (``tpsrhs_transfer``; ``utils/pfield_interpolate.cpp:138-146``
+        and ``CycleAvgJouleCoupling``): ``field`` is a float64 CUDA tensor of ``nrows * src_op.NDofs`` entries (byNODES);
+        returns ``(tensor (nrows, NDofs), num_missing)``.  Nodes outside the mesh of ``src_op`` get ``fill`` in every row
+        and are counted.  The first call for a pair of operators locates the nodes on the device and keeps the result on
+        ``src_op``; later calls only evaluate.  Meshes, orders and bases may differ; the dimension may not."""
+        if not isinstance(src_op, RHSoperator) or not getattr(src_op, "_h", None) or not getattr(self, "_h", None):
+            raise ValueError("expected a live RHSoperator as the source")
+        nrows = src_op._rows(field)
+        out = torch.empty((nrows, self.NDofs), dtype=torch.float64, device=field.device)
+        missing = C.c_int64(0)
+        st = self._lib.tpsrhs_transfer(src_op._h, self._h, nrows, C.c_void_p(field.data_ptr()), C.c_void_p(out.data_ptr()),
+                                       float(tol), float(fill), C.byref(missing))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_transfer")
+        return out, missing.value
+
+    def transferStats(self):
+        """``(located, cache hits)`` of the ``tpsrhs_transfer`` calls with this operator as the source: how many located
+        the target's nodes (ran ``k_locate``) and how many found a sampler from an earlier call."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        st = self._lib.tpsrhs_transfer_stats(self._h, C.byref(a), C.byref(b))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_transfer_stats")
+        return a.value, b.value
 
     def configureProbes(self, sampler, interval: int, capacity: int):
         """Probe records inside :meth:`advance`: after every step a counter goes up (zeroed here), and when it is a
@@ -488,11 +527,22 @@ class PointSampler:
     def __init__(self, op: RHSoperator, xyz, tol: float = 0.0, fill: float = 0.0):
         self._lib = capi.load()
         self._op = op
+        s = C.c_void_p()
+        if isinstance(xyz, torch.Tensor) and xyz.is_cuda:  # located on the device, in the caller's order
+            if xyz.dtype != torch.float64 or not xyz.is_contiguous() or xyz.dim() != 2 or xyz.shape[0] != op.dim:
+                raise ValueError("expected the points as a contiguous float64 CUDA tensor (dim, npts)")
+            self.npts = int(xyz.shape[1])
+            st = self._lib.tpsrhs_sampler_create_device(op._h, self.npts, C.c_void_p(xyz.data_ptr()), float(tol), float(fill),
+                                                        C.byref(s))
+            if st != 0:
+                raise TpsRhsError(st, "tpsrhs_sampler_create_device")
+            self._xyz = xyz  # read on the operator's stream: alive at least as long as the sampler
+            self._s = s
+            return
         xyz = np.ascontiguousarray(xyz, dtype=np.float64)
         if xyz.ndim != 2 or xyz.shape[0] != op.dim:
             raise ValueError("expected the points as an array (dim, npts)")
         self.npts = int(xyz.shape[1])
-        s = C.c_void_p()
         st = self._lib.tpsrhs_sampler_create(op._h, self.npts, xyz.ctypes.data, float(tol), float(fill), C.byref(s))
         if st != 0:
             raise TpsRhsError(st, "tpsrhs_sampler_create")
