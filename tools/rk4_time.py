@@ -3,7 +3,10 @@
 rk4 goes through rk4_step, the others through step (tpsrhs_step); every step returns to the host, as a driver's loop does.
     python tools/rk4_time.py --advance [--stats-interval K] ...
 times the steps inside ONE advance call instead (tpsrhs_advance / tpsrhs_advance_with on a side stream, constant dt, the
-captured step graph), with the running statistics sampled every K steps (0: off), and one add_sample on its own."""
+captured step graph), with the running statistics sampled every K steps (0: off), and one add_sample on its own.
+    python tools/rk4_time.py --advance --probe-interval 1 --monitor-interval 1 ...
+adds a probe record (8 points) and / or a monitor record every K steps, with room for every record: at K = 1 the
+between-step hooks run after every step, the case where their host side shows."""
 import argparse
 import os
 import sys
@@ -24,6 +27,8 @@ ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--dt", type=float, default=None, help="default: 1e-7 (cfg2), 1e-10 (the others: stiff chemistry)")
 ap.add_argument("--advance", action="store_true", help="time the steps of one advance call (the device loop)")
 ap.add_argument("--stats-interval", type=int, default=0, help="--advance: sample the running statistics every K steps")
+ap.add_argument("--probe-interval", type=int, default=0, help="--advance: a probe record of 8 points every K steps")
+ap.add_argument("--monitor-interval", type=int, default=0, help="--advance: a monitor record every K steps")
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
 
@@ -50,14 +55,27 @@ y = torch.empty_like(x)
 if args.advance:
     if args.stats_interval:
         op.configureStatistics(args.stats_interval)
+    if args.probe_interval:
+        nodes = op.nodeCoordinates().cpu().numpy()
+        sampler = op.createSampler(nodes[:, :: max(1, nodes.shape[1] // 8)][:, :8].copy())
+        op.configureProbes(sampler, args.probe_interval, args.steps + 4)
+    if args.monitor_interval:
+        op.configureMonitor(args.monitor_interval, args.steps + 4)
     t, _, _ = op.advance(x, 0.0, dt, 4, True, integrator=args.integrator)  # allocations, the capture
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     t, _, bad = op.advance(x, t, dt, args.steps, True, integrator=args.integrator)
     torch.cuda.synchronize()
     el = (time.perf_counter() - t0) / args.steps
-    line = (f"{args.workload} {args.integrator} advance, statistics every {args.stats_interval or 'never'}: step ms {el * 1e3:.4f}  "
+    line = (f"{args.workload} {args.integrator} advance, statistics every {args.stats_interval or 'never'}, probes every "
+            f"{args.probe_interval or 'never'}, monitor every {args.monitor_interval or 'never'}: step ms {el * 1e3:.4f}  "
             f"NaN {bad}  finite {bool(torch.isfinite(x).all())}")
+    if args.probe_interval:
+        iters, _, values, dropped = op.readProbes()
+        line += f"  probe records {len(iters)} dropped {dropped} finite {bool((values == values).all())}"
+    if args.monitor_interval:
+        rec = op.readMonitor()
+        line += f"  monitor records {len(rec['iters'])} dropped {rec['ndropped']}"
     if args.stats_interval:
         for _ in range(3):
             op.addSample(x)

@@ -28,20 +28,24 @@
 #include <vector>
 
 #include "../../include/tpsrhs.h"
+#include "device_buffer.hpp"
 #include "quadrature_points.hpp"
+#include "record_log.hpp"
+
+// the monitor records (tpsrhs_monitor_configure); cadence.interval 0: off
+struct tpsrhs_monitor_log {
+  tpsrhs::StepCadence cadence;  // count: steps of tpsrhs_advance / tpsrhs_advance_with since tpsrhs_monitor_configure
+  tpsrhs::RecordIndex index;
+  DevBuf<double> d_times, d_dts;            // [capacity], copied from d_ctl on the stream
+  DevBuf<double> d_totals, d_mins, d_maxs;  // [capacity][neq]
+};
 
 // behind tpsrhs_operator::integrals; owned by tpsrhs.hip (created at the first use, freed by tpsrhs_destroy)
 struct tpsrhs_integrals_state {
   int integ_blocks = 0, integ_run = 0, integ_eb = 1;  // grid, elements per block (a multiple of integ_eb), segments
   int stat_blocks = 0, stat_run = 0, stat_lpe = 64;
-  double *d_partial = nullptr;  // [INTEG_ROWS][max(2 * integ_blocks * integ_eb, 3 * stat_blocks * stat_eb)]
-  // monitor records (tpsrhs_monitor_configure); interval 0: off
-  int64_t interval = 0, capacity = 0;
-  int64_t count = 0;  // steps of tpsrhs_advance / tpsrhs_advance_with since tpsrhs_monitor_configure
-  int64_t nrecords = 0, ndropped = 0;
-  std::vector<int64_t> iters;  // [nrecords] `count` at each record
-  double *d_times = nullptr, *d_dts = nullptr;                          // [capacity], copied from d_ctl on the stream
-  double *d_totals = nullptr, *d_mins = nullptr, *d_maxs = nullptr;  // [capacity][neq]
+  DevBuf<double> d_partial;  // [INTEG_ROWS][max(2 * integ_blocks * integ_eb, 3 * stat_blocks * stat_eb)]
+  tpsrhs_monitor_log monitor;
 };
 
 namespace tpsrhs {

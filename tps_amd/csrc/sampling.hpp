@@ -13,10 +13,13 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <memory>
 #include <vector>
 
 #include "../../include/tpsrhs.h"
+#include "device_buffer.hpp"
 #include "point_locate.hpp"
+#include "record_log.hpp"
 
 struct tpsrhs_operator;
 
@@ -28,22 +31,22 @@ struct tpsrhs_sampler {
   std::vector<int32_t> elem;  // [npts], the caller's order; -1: not found
   std::vector<double> ref;    // [dim][npts], the caller's order
   // device, SORTED by element (the points that were not found last): neighbouring lanes read the same element
-  int32_t *d_elem = nullptr;  // [npts]
-  double *d_ref = nullptr;    // [dim][npts]
-  int64_t *d_perm = nullptr;  // [npts] sorted position -> the caller's index
+  DevBuf<int32_t> d_elem;  // [npts]
+  DevBuf<double> d_ref;    // [dim][npts]
+  DevBuf<int64_t> d_perm;  // [npts] sorted position -> the caller's index
   // tpsrhs_sampler_create_device: located by k_locate (locate_device.hpp), in the caller's order (d_perm is the identity);
   // nfound, elem and ref above are copied from the device the first time they are asked for
   bool on_device = false, host_valid = true;
-  unsigned long long *d_nfound = nullptr;
+  DevBuf<unsigned long long> d_nfound;
 };
 
 // one uploaded search grid (point_locate.hpp: LocateGrid) of the operator's mesh; the element boxes depend on the tolerance
 struct tpsrhs_locate_grid_dev {
   double tol = 0.0;
   tpsrhs::LocateGrid host;  // the scalars; its vectors are emptied after the upload
-  double *d_lo = nullptr, *d_hi = nullptr;
-  int64_t *d_start = nullptr;
-  int32_t *d_list = nullptr;
+  DevBuf<double> d_lo, d_hi;
+  DevBuf<int64_t> d_start;
+  DevBuf<int32_t> d_list;
 };
 
 // tpsrhs_transfer: the sampler on this operator (the source) at the nodes of `dst`
@@ -53,19 +56,21 @@ struct tpsrhs_transfer_entry {
   tpsrhs_sampler *sampler = nullptr;
 };
 
+// the probe records (tpsrhs_probe_configure); sampler NULL: off
+struct tpsrhs_probe_log {
+  tpsrhs_sampler *sampler = nullptr;
+  tpsrhs::StepCadence cadence;  // count: steps of tpsrhs_advance / tpsrhs_advance_with since tpsrhs_probe_configure
+  tpsrhs::RecordIndex index;
+  DevBuf<double> d_values;  // [capacity][neq][npts]
+  DevBuf<double> d_times;   // [capacity], copied from d_ctl[1] on the stream
+};
+
 // behind tpsrhs_operator::sampling; owned by tpsrhs.hip
 struct tpsrhs_sampling_state {
-  std::vector<tpsrhs_sampler *> samplers;
-  // probes (tpsrhs_probe_configure); sampler NULL: off
-  tpsrhs_sampler *probe = nullptr;
-  int64_t interval = 0, capacity = 0;
-  int64_t count = 0;                 // steps of tpsrhs_advance / tpsrhs_advance_with since tpsrhs_probe_configure
-  int64_t nrecords = 0, ndropped = 0;
-  std::vector<int64_t> iters;        // [nrecords] `count` at each record: the host issues every step and knows it
-  double *d_values = nullptr;        // [capacity][neq][npts]
-  double *d_times = nullptr;         // [capacity], copied from d_ctl[1] on the stream
+  std::vector<std::unique_ptr<tpsrhs_sampler>> samplers;
+  tpsrhs_probe_log probe;
   // device location (tpsrhs_sampler_create_device): one grid per tolerance, uploaded at first use
-  std::vector<tpsrhs_locate_grid_dev *> grids;
+  std::vector<std::unique_ptr<tpsrhs_locate_grid_dev>> grids;
   // tpsrhs_transfer with this operator as the source: one sampler per (dst, tol), and how often it was made / found
   std::vector<tpsrhs_transfer_entry> transfers;
   int64_t num_located = 0, num_cache_hits = 0;

@@ -28,14 +28,18 @@
 
 #include <cstdint>
 
+#include "device_buffer.hpp"
+#include "record_log.hpp"
+
 // behind tpsrhs_operator::stats (tpsrhs_stats_configure); owned by tpsrhs.hip
 struct tpsrhs_stats_state {
-  int64_t sample_interval = 0, start_iter = 0;  // the reference's sampleFreq and startIter
-  int64_t iter = 0;                             // steps taken by tpsrhs_advance / tpsrhs_advance_with (+ tpsrhs_stats_set_iter)
+  // interval, start: the reference's sampleFreq and startIter; count: the steps taken by tpsrhs_advance /
+  // tpsrhs_advance_with (+ tpsrhs_stats_set_iter)
+  tpsrhs::StepCadence cadence;
   int ns_mean = 0, ns_vari = 0;
   int nvar = 0;  // 0: no covariances
-  double *d_mean = nullptr, *d_vari = nullptr;
-  double *d_scratch = nullptr;  // [neq + 1][ndofs]: the primitives and the pressure of the sampled state
+  DevBuf<double> d_mean, d_vari;
+  DevBuf<double> d_scratch;  // [neq + 1][ndofs]: the primitives and the pressure of the sampled state
 };
 
 namespace tpsrhs {

@@ -4,6 +4,7 @@
 // HBM, and enqueues the three sweeps of kernels.hpp on one HIP stream per operator.  There is no
 // CPU fallback: without a HIP device tpsrhs_create returns TPSRHS_ERR_NO_DEVICE.
 #include "operator.hpp"
+#include "device_buffer.hpp"
 #include "integrals.hpp"
 #include "locate_device.hpp"
 #include "physics_dryair.hpp"
@@ -11,6 +12,7 @@
 #include "physics_plasma.hpp"
 #include "plasma_params_host.hpp"
 #include "point_locate.hpp"
+#include "record_log.hpp"
 #include "sampling.hpp"
 #include "statistics.hpp"
 #include "time_integrators.hpp"
@@ -24,6 +26,7 @@
 #include <mutex>
 #include <new>
 #include <thread>
+#include <type_traits>
 
 // The plasma kernel families (plasma_family.hpp) are shared objects of their own, libtpsrhs_<unit>.so next to this library,
 // loaded when an operator of that family is created: load_family below.
@@ -650,55 +653,45 @@ int guarded(F &&f) {
 // Running statistics (statistics.hpp): at the end of this file
 void stats_release(tpsrhs_operator *h);
 void stats_sample(tpsrhs_operator *h, const double *x);
-// the time loop has taken one more step: count it and, at a sampling point, enqueue a sample of x
-inline void stats_after_step(tpsrhs_operator *h, const double *x) {
-  tpsrhs_stats_state *st = h->stats;
-  if (!st) return;
-  st->iter++;
-  if (st->iter % st->sample_interval == 0 && st->iter >= st->start_iter) stats_sample(h, x);
-}
-// would a sample fall after the first of the next two steps?
-inline bool stats_due_after_next(const tpsrhs_operator *h) {
-  const tpsrhs_stats_state *st = h->stats;
-  return st && (st->iter + 1) % st->sample_interval == 0 && st->iter + 1 >= st->start_iter;
-}
 // Probe records (sampling.hpp): at the end of this file
 void sampling_release(tpsrhs_operator *h);
 void transfer_release(tpsrhs_operator *h);
 void probe_record(tpsrhs_operator *h, const double *x);
-// the same two questions for the probes: count the step and enqueue a record when one is due / is one due after the next step?
-inline void probe_after_step(tpsrhs_operator *h, const double *x) {
-  tpsrhs_sampling_state *ss = h->sampling;
-  if (!ss || !ss->probe) return;
-  ss->count++;
-  if (ss->count % ss->interval == 0) probe_record(h, x);
-}
-inline bool probe_due_after_next(const tpsrhs_operator *h) {
-  const tpsrhs_sampling_state *ss = h->sampling;
-  return ss && ss->probe && (ss->count + 1) % ss->interval == 0;
-}
 // Monitor records (integrals.hpp): at the end of this file
 void integrals_release(tpsrhs_operator *h);
 void monitor_record(tpsrhs_operator *h, const double *x);
-inline void monitor_after_step(tpsrhs_operator *h, const double *x) {
-  tpsrhs_integrals_state *is = h->integrals;
-  if (!is || !is->interval) return;
-  is->count++;
-  if (is->count % is->interval == 0) monitor_record(h, x);
-}
-inline bool monitor_due_after_next(const tpsrhs_operator *h) {
-  const tpsrhs_integrals_state *is = h->integrals;
-  return is && is->interval && (is->count + 1) % is->interval == 0;
-}
-// What the time loop does between two steps, and whether any of it falls between the next two: everything that reads x
-// between steps goes through these two, so that the loop itself knows nothing about statistics, probes or the monitor.
+// What the time loop does between two steps, and whether any of it falls after the first of the next two: everything that
+// reads x between steps goes through these two, so that the loop itself knows nothing about statistics, probes or the
+// monitor.  Each observer has one StepCadence (record_log.hpp; interval 0: off), which answers both questions.
 inline void after_step(tpsrhs_operator *h, const double *x) {
-  stats_after_step(h, x);
-  probe_after_step(h, x);
-  monitor_after_step(h, x);
+  if (h->stats && h->stats->cadence.tick()) stats_sample(h, x);
+  if (h->sampling && h->sampling->probe.cadence.tick()) probe_record(h, x);
+  if (h->integrals && h->integrals->monitor.cadence.tick()) monitor_record(h, x);
 }
 inline bool work_due_after_next(const tpsrhs_operator *h) {
-  return stats_due_after_next(h) || probe_due_after_next(h) || monitor_due_after_next(h);
+  return (h->stats && h->stats->cadence.due_after_next()) || (h->sampling && h->sampling->probe.cadence.due_after_next()) ||
+         (h->integrals && h->integrals->monitor.cadence.due_after_next());
+}
+
+// f(std::integral_constant<int, DIM>, std::integral_constant<int, P>) for the operator's dim and order: the (dim, order) pairs
+// the post-processing kernels of this unit are built for, listed once
+template <int N>
+using int_c = std::integral_constant<int, N>;
+template <class F>
+void with_dim_order(const tpsrhs_operator *h, const char *who, F &&f) {
+  switch (h->dim * 10 + h->order) {
+    case 21: f(int_c<2>(), int_c<1>()); break;
+    case 22: f(int_c<2>(), int_c<2>()); break;
+    case 23: f(int_c<2>(), int_c<3>()); break;
+    case 24: f(int_c<2>(), int_c<4>()); break;
+    case 25: f(int_c<2>(), int_c<5>()); break;
+    case 31: f(int_c<3>(), int_c<1>()); break;
+    case 32: f(int_c<3>(), int_c<2>()); break;
+    case 33: f(int_c<3>(), int_c<3>()); break;
+    case 34: f(int_c<3>(), int_c<4>()); break;
+    case 35: f(int_c<3>(), int_c<5>()); break;
+    default: throw Unsupported(std::string(who) + ": dim 2 or 3 and polynomial orders 1..5 are built");
+  }
 }
 
 }  // namespace
@@ -1039,6 +1032,11 @@ void upload_forcing(tpsrhs_operator *h) {
   HIP_CHECK(hipStreamSynchronize(h->stream));  // an earlier Mult may still read the block
   HIP_CHECK(hipMemcpy(h->d_forcing, &h->forcing, sizeof(ForcingDev), hipMemcpyHostToDevice));
 }
+
+// the buffers of one forcing's mixed-out zones, in the form tpsrhs_operator::d_mixed_out keeps them
+void free_mixed_out(const std::vector<void *> &v) {
+  for (void *q : v) (void)hipFree(q);
+}
 }  // namespace
 
 int tpsrhs_set_forcing(tpsrhs_handle h, const tpsrhs_forcing *in) {
@@ -1053,8 +1051,7 @@ int tpsrhs_set_forcing(tpsrhs_handle h, const tpsrhs_forcing *in) {
       std::vector<void *> &v;
       bool keep = false;
       ~Guard() {
-        if (!keep)
-          for (void *q : v) (void)hipFree(q);
+        if (!keep) free_mixed_out(v);
       }
     } guard{fresh};
     if (in) {
@@ -1186,7 +1183,7 @@ int tpsrhs_set_forcing(tpsrhs_handle h, const tpsrhs_forcing *in) {
     h->d_mixed_out = fresh;
     guard.keep = true;
     h->config_epoch++;
-    for (void *q : old) (void)hipFree(q);
+    free_mixed_out(old);
   });
 }
 
@@ -1473,8 +1470,6 @@ void stats_release(tpsrhs_operator *h) {
   if (!st) return;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);  // a sample may still be running
-  for (double *p : {st->d_mean, st->d_vari, st->d_scratch})
-    if (p) (void)hipFree(p);
   delete st;
   h->stats = nullptr;
 }
@@ -1483,18 +1478,19 @@ template <int NVEL, bool VARI>
 void launch_stats_sample(tpsrhs_operator *h) {
   tpsrhs_stats_state *st = h->stats;
   const int64_t n = h->ndofs;
-  const double *prim = st->d_scratch, *p = st->d_scratch + h->neq * n;
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(prim) | reinterpret_cast<uintptr_t>(st->d_mean) | reinterpret_cast<uintptr_t>(st->d_vari);
+  const double *prim = st->d_scratch.get(), *p = prim + h->neq * n;
+  double *mean = st->d_mean.get(), *vari = st->d_vari.get();
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(prim) | reinterpret_cast<uintptr_t>(mean) | reinterpret_cast<uintptr_t>(vari);
   const bool vec = (n & 1) == 0 && (bits & 15) == 0;  // then every row of every array is 16-byte aligned, p included
   const int64_t items = vec ? n / 2 : n;
   const int grid = static_cast<int>(std::min<int64_t>((items + 255) / 256, 8192));  // the grid cap of k_rk_stage
   if (grid == 0) return;
   if (vec)
     hipLaunchKernelGGL((k_stats_sample<NVEL, VARI, true, 256>), dim3(grid), dim3(256), 0, h->stream, h->neq, n, st->ns_mean,
-                       st->ns_vari, prim, p, st->d_mean, st->d_vari);
+                       st->ns_vari, prim, p, mean, vari);
   else
     hipLaunchKernelGGL((k_stats_sample<NVEL, VARI, false, 256>), dim3(grid), dim3(256), 0, h->stream, h->neq, n, st->ns_mean,
-                       st->ns_vari, prim, p, st->d_mean, st->d_vari);
+                       st->ns_vari, prim, p, mean, vari);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -1503,8 +1499,8 @@ void launch_stats_sample(tpsrhs_operator *h) {
 void stats_sample(tpsrhs_operator *h, const double *x) {
   tpsrhs_stats_state *st = h->stats;
   const int64_t n = h->ndofs;
-  h->point_eval(h, 0, n, x, st->d_scratch);
-  h->point_eval(h, 1, n, x, st->d_scratch + h->neq * n);
+  h->point_eval(h, 0, n, x, st->d_scratch.get());
+  h->point_eval(h, 1, n, x, st->d_scratch.get() + h->neq * n);
   const bool vari = st->nvar > 0;
   if (h->nvel == 3)
     vari ? launch_stats_sample<3, true>(h) : launch_stats_sample<3, false>(h);
@@ -1538,16 +1534,16 @@ int tpsrhs_stats_configure(tpsrhs_handle h, int64_t sample_interval, int64_t sta
     if (sample_interval == 0) return;
     HIP_CHECK(hipSetDevice(h->device));
     std::unique_ptr<tpsrhs_stats_state> st(new tpsrhs_stats_state());
-    st->sample_interval = sample_interval;
-    st->start_iter = start_iter;
+    st->cadence.interval = sample_interval;
+    st->cadence.start = start_iter;
     st->nvar = compute_variances ? h->nvel * (h->nvel + 1) / 2 : 0;
     const int64_t n = h->ndofs;
-    h->stats = st.release();  // from here on stats_release frees what was allocated
-    h->stats->d_mean = dev_alloc<double>(h->neq * n);
-    if (h->stats->nvar) h->stats->d_vari = dev_alloc<double>(h->stats->nvar * n);
-    h->stats->d_scratch = dev_alloc<double>((h->neq + 1) * n);
-    HIP_CHECK(hipMemsetAsync(h->stats->d_mean, 0, sizeof(double) * h->neq * n, h->stream));
-    if (h->stats->nvar) HIP_CHECK(hipMemsetAsync(h->stats->d_vari, 0, sizeof(double) * h->stats->nvar * n, h->stream));
+    st->d_mean = DevBuf<double>(h->neq * n);
+    if (st->nvar) st->d_vari = DevBuf<double>(st->nvar * n);
+    st->d_scratch = DevBuf<double>((h->neq + 1) * n);
+    HIP_CHECK(hipMemsetAsync(st->d_mean.get(), 0, sizeof(double) * h->neq * n, h->stream));
+    if (st->nvar) HIP_CHECK(hipMemsetAsync(st->d_vari.get(), 0, sizeof(double) * st->nvar * n, h->stream));
+    h->stats = st.release();  // complete: a call that throws above leaves the statistics off
   });
 }
 
@@ -1555,7 +1551,7 @@ int tpsrhs_stats_set_iter(tpsrhs_handle h, int64_t iter) {
   tpsrhs_stats_state *st = stats_of(h, "tpsrhs_stats_set_iter");
   if (!st) return TPSRHS_ERR_INVALID_ARGUMENT;
   if (iter < 0) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_set_iter: needs iter >= 0");
-  st->iter = iter;
+  st->cadence.count = iter;
   return TPSRHS_OK;
 }
 
@@ -1576,11 +1572,11 @@ int tpsrhs_stats_get(tpsrhs_handle h, double *mean_out, double *vari_out, int *n
   return guarded([&] {
     HIP_CHECK(hipSetDevice(h->device));
     const int64_t n = h->ndofs;
-    if (mean_out) HIP_CHECK(hipMemcpyAsync(mean_out, st->d_mean, sizeof(double) * h->neq * n, hipMemcpyDeviceToDevice, h->stream));
-    if (vari_out) HIP_CHECK(hipMemcpyAsync(vari_out, st->d_vari, sizeof(double) * st->nvar * n, hipMemcpyDeviceToDevice, h->stream));
+    if (mean_out) HIP_CHECK(hipMemcpyAsync(mean_out, st->d_mean.get(), sizeof(double) * h->neq * n, hipMemcpyDeviceToDevice, h->stream));
+    if (vari_out) HIP_CHECK(hipMemcpyAsync(vari_out, st->d_vari.get(), sizeof(double) * st->nvar * n, hipMemcpyDeviceToDevice, h->stream));
     if (ns_mean) *ns_mean = st->ns_mean;
     if (ns_vari) *ns_vari = st->ns_vari;
-    if (iter) *iter = st->iter;
+    if (iter) *iter = st->cadence.count;
   });
 }
 
@@ -1596,14 +1592,14 @@ int tpsrhs_stats_set(tpsrhs_handle h, const double *mean, const double *vari, in
     const int64_t n = h->ndofs;
     const bool keep_vari = vari && ns_vari > 0;  // else restartRMS: the covariances start again
     if (ns_mean > 0)
-      HIP_CHECK(hipMemcpyAsync(st->d_mean, mean, sizeof(double) * h->neq * n, hipMemcpyDeviceToDevice, h->stream));
+      HIP_CHECK(hipMemcpyAsync(st->d_mean.get(), mean, sizeof(double) * h->neq * n, hipMemcpyDeviceToDevice, h->stream));
     else
-      HIP_CHECK(hipMemsetAsync(st->d_mean, 0, sizeof(double) * h->neq * n, h->stream));
+      HIP_CHECK(hipMemsetAsync(st->d_mean.get(), 0, sizeof(double) * h->neq * n, h->stream));
     if (st->nvar) {
       if (keep_vari)
-        HIP_CHECK(hipMemcpyAsync(st->d_vari, vari, sizeof(double) * st->nvar * n, hipMemcpyDeviceToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(st->d_vari.get(), vari, sizeof(double) * st->nvar * n, hipMemcpyDeviceToDevice, h->stream));
       else
-        HIP_CHECK(hipMemsetAsync(st->d_vari, 0, sizeof(double) * st->nvar * n, h->stream));
+        HIP_CHECK(hipMemsetAsync(st->d_vari.get(), 0, sizeof(double) * st->nvar * n, h->stream));
     }
     st->ns_mean = ns_mean;
     st->ns_vari = keep_vari ? ns_vari : 0;
@@ -1623,35 +1619,25 @@ int tpsrhs_stats_num_variances(tpsrhs_handle h, int *num_variances) {
 // ---- point sampling and probe records (sampling.hpp, point_locate.hpp) --------------------------------------------------------
 // After every other launch of this unit, as the integrators and the statistics above.
 namespace {
-void sampler_free(tpsrhs_sampler *s) {
-  if (s->d_elem) (void)hipFree(s->d_elem);
-  if (s->d_ref) (void)hipFree(s->d_ref);
-  if (s->d_perm) (void)hipFree(s->d_perm);
-  if (s->d_nfound) (void)hipFree(s->d_nfound);
-  delete s;
+// What reading the probe records and reading the monitor records share.  The first n rows of one column of a log (`width`
+// doubles a row) to the host, on the operator's stream ...
+void fetch_rows(tpsrhs_operator *h, double *dst, const DevBuf<double> &col, int64_t n, int64_t width) {
+  if (dst && n * width) HIP_CHECK(hipMemcpyAsync(dst, col.get(), sizeof(double) * n * width, hipMemcpyDeviceToHost, h->stream));
 }
-
-void locate_grid_free(tpsrhs_locate_grid_dev *g) {
-  if (g->d_lo) (void)hipFree(g->d_lo);
-  if (g->d_hi) (void)hipFree(g->d_hi);
-  if (g->d_start) (void)hipFree(g->d_start);
-  if (g->d_list) (void)hipFree(g->d_list);
-  delete g;
+// ... and, once the stream has been synchronised, the host half: the counters, the step of every record, the optional restart
+void read_index(RecordIndex &ix, int64_t *nrecords, int64_t *ndropped, int64_t *iters_out, int reset) {
+  if (nrecords) *nrecords = ix.nrecords;
+  if (ndropped) *ndropped = ix.ndropped;
+  if (iters_out && ix.nrecords) std::memcpy(iters_out, ix.iters.data(), sizeof(int64_t) * ix.nrecords);
+  if (reset) ix.reset();  // the buffer starts again; the step counter goes on
 }
 
 void probe_off(tpsrhs_operator *h) {
   tpsrhs_sampling_state *ss = h->sampling;
-  if (!ss) return;
-  if (ss->d_values || ss->d_times) {
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);  // a record may still be running
-    if (ss->d_values) (void)hipFree(ss->d_values);
-    if (ss->d_times) (void)hipFree(ss->d_times);
-  }
-  ss->d_values = ss->d_times = nullptr;
-  ss->probe = nullptr;
-  ss->interval = ss->capacity = ss->count = ss->nrecords = ss->ndropped = 0;
-  ss->iters.clear();
+  if (!ss || !ss->probe.sampler) return;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);  // a record may still be running
+  ss->probe = tpsrhs_probe_log();
 }
 
 void sampling_release(tpsrhs_operator *h) {
@@ -1659,9 +1645,6 @@ void sampling_release(tpsrhs_operator *h) {
   if (!ss) return;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);  // a sample may still be running
-  probe_off(h);
-  for (tpsrhs_sampler *s : ss->samplers) sampler_free(s);
-  for (tpsrhs_locate_grid_dev *g : ss->grids) locate_grid_free(g);
   delete ss;
   h->sampling = nullptr;
 }
@@ -1696,7 +1679,7 @@ void launch_sample(tpsrhs_operator *h, const tpsrhs_sampler *s, const SampleNode
   if (grid == 0) return;
   if (grid >= (int64_t(1) << 31)) throw Unsupported("tpsrhs_sample: more than 2^37 points");
   hipLaunchKernelGGL((k_sample<DIM, P, BLOCK>), dim3(static_cast<unsigned>(grid)), dim3(BLOCK), 0, h->stream, s->npts, nrows,
-                     h->ndofs, nodes, s->d_elem, s->d_ref, s->d_perm, s->fill, field, out);
+                     h->ndofs, nodes, s->d_elem.get(), s->d_ref.get(), s->d_perm.get(), s->fill, field, out);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -1705,34 +1688,24 @@ void sample_field(tpsrhs_operator *h, const tpsrhs_sampler *s, int nrows, const 
   SampleNodes nodes = {};
   double wts[TPSRHS_MAXORDER + 1];
   segment_rule01(h->nc, h->order + 1, nodes.x, wts);  // the nodes of the operator's basis, as make_tables places them
-  const int key = h->dim * 10 + h->order;
-  switch (key) {
-    case 21: launch_sample<2, 1>(h, s, nodes, nrows, field, out); break;
-    case 22: launch_sample<2, 2>(h, s, nodes, nrows, field, out); break;
-    case 23: launch_sample<2, 3>(h, s, nodes, nrows, field, out); break;
-    case 24: launch_sample<2, 4>(h, s, nodes, nrows, field, out); break;
-    case 25: launch_sample<2, 5>(h, s, nodes, nrows, field, out); break;
-    case 31: launch_sample<3, 1>(h, s, nodes, nrows, field, out); break;
-    case 32: launch_sample<3, 2>(h, s, nodes, nrows, field, out); break;
-    case 33: launch_sample<3, 3>(h, s, nodes, nrows, field, out); break;
-    case 34: launch_sample<3, 4>(h, s, nodes, nrows, field, out); break;
-    case 35: launch_sample<3, 5>(h, s, nodes, nrows, field, out); break;
-    default: throw Unsupported("tpsrhs_sample: dim 2 or 3 and polynomial orders 1..5 are built");
-  }
+  with_dim_order(h, "tpsrhs_sample", [&](auto dim, auto p) {
+    launch_sample<decltype(dim)::value, decltype(p)::value>(h, s, nodes, nrows, field, out);
+  });
 }
 
 // One probe record of the device vector x, stream-ordered, or one more dropped record when the buffer is full.
 void probe_record(tpsrhs_operator *h, const double *x) {
-  tpsrhs_sampling_state *ss = h->sampling;
-  if (ss->nrecords >= ss->capacity) {
-    ss->ndropped++;
-    return;
-  }
-  const int64_t r = ss->nrecords, per = static_cast<int64_t>(h->neq) * ss->probe->npts;
-  sample_field(h, ss->probe, h->neq, x, ss->d_values + r * per);
-  HIP_CHECK(hipMemcpyAsync(ss->d_times + r, h->d_ctl + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  ss->iters.push_back(ss->count);
-  ss->nrecords++;
+  tpsrhs_probe_log &log = h->sampling->probe;
+  const int64_t r = log.index.claim(log.cadence.count);
+  if (r < 0) return;
+  const int64_t per = static_cast<int64_t>(h->neq) * log.sampler->npts;
+  sample_field(h, log.sampler, h->neq, x, log.d_values.get() + r * per);
+  HIP_CHECK(hipMemcpyAsync(log.d_times.get() + r, h->d_ctl + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+}
+
+// the position of s among the samplers of ss, or their end
+auto sampler_find(tpsrhs_sampling_state *ss, const tpsrhs_sampler *s) {
+  return std::find_if(ss->samplers.begin(), ss->samplers.end(), [s](const auto &u) { return u.get() == s; });
 }
 
 // s, a live sampler of h, leaves it
@@ -1740,9 +1713,8 @@ void sampler_remove(tpsrhs_operator *h, tpsrhs_sampler *s) {
   tpsrhs_sampling_state *ss = h->sampling;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);  // a sample may still be running
-  if (ss->probe == s) probe_off(h);
-  ss->samplers.erase(std::find(ss->samplers.begin(), ss->samplers.end(), s));
-  sampler_free(s);
+  if (ss->probe.sampler == s) probe_off(h);
+  ss->samplers.erase(sampler_find(ss, s));
 }
 
 // The host copies of a device-located sampler (elem, ref, nfound), fetched once; synchronises the stream.
@@ -1753,10 +1725,10 @@ void sampler_fetch(tpsrhs_sampler *s) {
   unsigned long long nf = 0;
   s->elem.resize(static_cast<size_t>(s->npts));
   s->ref.resize(static_cast<size_t>(s->npts) * h->dim);
-  HIP_CHECK(hipMemcpyAsync(&nf, s->d_nfound, sizeof(nf), hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(hipMemcpyAsync(&nf, s->d_nfound.get(), sizeof(nf), hipMemcpyDeviceToHost, h->stream));
   if (s->npts) {
-    HIP_CHECK(hipMemcpyAsync(s->elem.data(), s->d_elem, s->elem.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipMemcpyAsync(s->ref.data(), s->d_ref, s->ref.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipMemcpyAsync(s->elem.data(), s->d_elem.get(), s->elem.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipMemcpyAsync(s->ref.data(), s->d_ref.get(), s->ref.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   }
   HIP_CHECK(hipStreamSynchronize(h->stream));
   s->nfound = static_cast<int64_t>(nf);
@@ -1767,7 +1739,7 @@ int64_t sampler_nfound(tpsrhs_sampler *s) {
   if (s->host_valid) return s->nfound;
   tpsrhs_operator *h = s->owner;
   unsigned long long nf = 0;
-  HIP_CHECK(hipMemcpyAsync(&nf, s->d_nfound, sizeof(nf), hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(hipMemcpyAsync(&nf, s->d_nfound.get(), sizeof(nf), hipMemcpyDeviceToHost, h->stream));
   HIP_CHECK(hipStreamSynchronize(h->stream));
   return static_cast<int64_t>(nf);
 }
@@ -1778,30 +1750,23 @@ LocateGridView<DIM> device_grid(tpsrhs_operator *h, double tol) {
   if (!h->sampling) h->sampling = new tpsrhs_sampling_state();
   tpsrhs_sampling_state *ss = h->sampling;
   tpsrhs_locate_grid_dev *g = nullptr;
-  for (tpsrhs_locate_grid_dev *c : ss->grids)
-    if (c->tol == tol) g = c;
+  for (const auto &c : ss->grids)
+    if (c->tol == tol) g = c.get();
   if (!g) {
     std::unique_ptr<tpsrhs_locate_grid_dev> up(new tpsrhs_locate_grid_dev());
     up->tol = tol;
     up->host = build_locate_grid<DIM>(h->ne, h->topo.verts.data(), tol);
-    struct Guard {
-      tpsrhs_locate_grid_dev *g;
-      ~Guard() {
-        if (g) locate_grid_free(g);
-      }
-    } guard{up.release()};
-    g = guard.g;
-    g->d_lo = dev_upload(g->host.lo);
-    g->d_hi = dev_upload(g->host.hi);
-    g->d_start = dev_upload(g->host.start);
-    g->d_list = dev_upload(g->host.list);
-    for (auto *v : {&g->host.lo, &g->host.hi}) std::vector<double>().swap(*v);
-    std::vector<int64_t>().swap(g->host.start);
-    std::vector<int32_t>().swap(g->host.list);
-    ss->grids.push_back(g);
-    guard.g = nullptr;
+    up->d_lo = DevBuf<double>(up->host.lo);
+    up->d_hi = DevBuf<double>(up->host.hi);
+    up->d_start = DevBuf<int64_t>(up->host.start);
+    up->d_list = DevBuf<int32_t>(up->host.list);
+    for (auto *v : {&up->host.lo, &up->host.hi}) std::vector<double>().swap(*v);
+    std::vector<int64_t>().swap(up->host.start);
+    std::vector<int32_t>().swap(up->host.list);
+    g = up.get();
+    ss->grids.push_back(std::move(up));
   }
-  return locate_grid_view<DIM>(g->host, g->d_lo, g->d_hi, g->d_start, g->d_list);
+  return locate_grid_view<DIM>(g->host, g->d_lo.get(), g->d_hi.get(), g->d_start.get(), g->d_list.get());
 }
 
 template <int DIM>
@@ -1810,10 +1775,10 @@ void launch_locate(tpsrhs_operator *h, tpsrhs_sampler *s, const double *xyz, dou
   const int64_t grid = (s->npts + BLOCK - 1) / BLOCK;
   if (grid >= (int64_t(1) << 31)) throw Unsupported("tpsrhs_sampler_create_device: more than 2^37 points");
   const LocateGridView<DIM> g = device_grid<DIM>(h, tol);
-  HIP_CHECK(hipMemsetAsync(s->d_nfound, 0, sizeof(unsigned long long), h->stream));
+  HIP_CHECK(hipMemsetAsync(s->d_nfound.get(), 0, sizeof(unsigned long long), h->stream));
   if (grid == 0) return;
   hipLaunchKernelGGL((k_locate<DIM, BLOCK>), dim3(static_cast<unsigned>(grid)), dim3(BLOCK), 0, h->stream, g, h->d_verts, s->npts,
-                     xyz, tol, s->d_elem, s->d_ref, s->d_perm, s->d_nfound);
+                     xyz, tol, s->d_elem.get(), s->d_ref.get(), s->d_perm.get(), s->d_nfound.get());
   HIP_CHECK(hipGetLastError());
 }
 
@@ -1821,29 +1786,22 @@ void launch_locate(tpsrhs_operator *h, tpsrhs_sampler *s, const double *xyz, dou
 tpsrhs_sampler *sampler_create_device(tpsrhs_operator *h, int64_t npts, const double *xyz, double tol, double fill) {
   if (h->ne <= 0) throw Unsupported("tpsrhs_sampler_create_device: the operator has no elements");
   const double t = tol > 0.0 ? tol : LOCATE_DEFAULT_TOL;
-  tpsrhs_sampler *s = new tpsrhs_sampler();
-  struct Guard {
-    tpsrhs_sampler *s;
-    ~Guard() {
-      if (s) sampler_free(s);
-    }
-  } guard{s};
+  std::unique_ptr<tpsrhs_sampler> s(new tpsrhs_sampler());
   s->owner = h;
   s->npts = npts;
   s->fill = fill;
   s->on_device = true;
   s->host_valid = false;
-  s->d_elem = dev_alloc<int32_t>(npts);
-  s->d_ref = dev_alloc<double>(npts * h->dim);
-  s->d_perm = dev_alloc<int64_t>(npts);
-  s->d_nfound = dev_alloc<unsigned long long>(1);
+  s->d_elem = DevBuf<int32_t>(npts);
+  s->d_ref = DevBuf<double>(npts * h->dim);
+  s->d_perm = DevBuf<int64_t>(npts);
+  s->d_nfound = DevBuf<unsigned long long>(1);
   if (h->dim == 2)
-    launch_locate<2>(h, s, xyz, t);
+    launch_locate<2>(h, s.get(), xyz, t);
   else
-    launch_locate<3>(h, s, xyz, t);
-  h->sampling->samplers.push_back(s);  // exists: device_grid made it
-  guard.s = nullptr;
-  return s;
+    launch_locate<3>(h, s.get(), xyz, t);
+  h->sampling->samplers.push_back(std::move(s));  // exists: device_grid made it
+  return h->sampling->samplers.back().get();
 }
 
 void node_coordinates_device(tpsrhs_operator *h, double *xyz_out, hipStream_t stream) {
@@ -1865,8 +1823,8 @@ void node_coordinates_device(tpsrhs_operator *h, double *xyz_out, hipStream_t st
 
 // is s a live sampler?  (its owner is then s->owner)
 bool sampler_alive(const tpsrhs_sampler *s, const tpsrhs_operator *h) {
-  const tpsrhs_sampling_state *ss = h ? h->sampling : nullptr;
-  return ss && std::find(ss->samplers.begin(), ss->samplers.end(), s) != ss->samplers.end();
+  tpsrhs_sampling_state *ss = h ? h->sampling : nullptr;
+  return ss && sampler_find(ss, s) != ss->samplers.end();
 }
 }  // namespace
 
@@ -1924,20 +1882,12 @@ int tpsrhs_sampler_create(tpsrhs_handle h, int64_t npts, const double *xyz, doub
       if (el[static_cast<size_t>(i)] >= 0) sp->nfound++;
       for (int d = 0; d < dim; d++) sref[static_cast<size_t>(k + d * npts)] = sp->ref[static_cast<size_t>(i + d * npts)];
     }
-    tpsrhs_sampler *s = sp.release();
-    struct Guard {
-      tpsrhs_sampler *s;
-      ~Guard() {
-        if (s) sampler_free(s);
-      }
-    } guard{s};
-    s->d_elem = dev_upload(selem);
-    s->d_ref = dev_upload(sref);
-    s->d_perm = dev_upload(perm);
+    sp->d_elem = DevBuf<int32_t>(selem);
+    sp->d_ref = DevBuf<double>(sref);
+    sp->d_perm = DevBuf<int64_t>(perm);
     if (!h->sampling) h->sampling = new tpsrhs_sampling_state();
-    h->sampling->samplers.push_back(s);
-    guard.s = nullptr;
-    *out = s;
+    h->sampling->samplers.push_back(std::move(sp));
+    *out = h->sampling->samplers.back().get();
   });
 }
 
@@ -2012,13 +1962,9 @@ int tpsrhs_transfer(tpsrhs_handle src, tpsrhs_handle dst, int nrows, const doubl
         src->sampling->num_cache_hits++;
       } else {
         // the nodes of dst, on src's stream (they depend on nothing dst's stream writes), live until they are located
-        double *xyz = dev_alloc<double>(static_cast<size_t>(dst->ndofs) * dst->dim);
-        struct Guard {
-          double *p;
-          ~Guard() { (void)hipFree(p); }
-        } guard{xyz};
-        node_coordinates_device(dst, xyz, src->stream);
-        s = sampler_create_device(src, dst->ndofs, xyz, t, fill);
+        const DevBuf<double> xyz(static_cast<size_t>(dst->ndofs) * dst->dim);
+        node_coordinates_device(dst, xyz.get(), src->stream);
+        s = sampler_create_device(src, dst->ndofs, xyz.get(), t, fill);
         HIP_CHECK(hipStreamSynchronize(src->stream));  // once per pair: xyz is freed below
         src->sampling->transfers.push_back({dst, t, s});
         src->sampling->num_located++;
@@ -2060,13 +2006,15 @@ int tpsrhs_probe_configure(tpsrhs_handle h, tpsrhs_sampler_handle s, int64_t int
     probe_off(h);
     if (!on) return;
     HIP_CHECK(hipSetDevice(h->device));
-    tpsrhs_sampling_state *ss = h->sampling;  // exists: s is one of its samplers
-    ss->d_values = dev_alloc<double>(capacity * h->neq * s->npts);
-    ss->d_times = dev_alloc<double>(capacity);
+    tpsrhs_probe_log log;
+    log.sampler = s;
+    log.cadence.interval = interval;
+    log.index.capacity = capacity;
+    log.d_values = DevBuf<double>(capacity * h->neq * s->npts);
+    log.d_times = DevBuf<double>(capacity);
     if (!h->d_ctl) h->d_ctl = dev_alloc<double>(3);  // the loop's {dt, time, max speed}: a record copies the time from there
-    ss->probe = s;
-    ss->interval = interval;
-    ss->capacity = capacity;
+    // complete: a call that throws above leaves the probes off.  (h->sampling exists: s is one of its samplers)
+    h->sampling->probe = std::move(log);
   });
 }
 
@@ -2074,21 +2022,14 @@ int tpsrhs_probe_read(tpsrhs_handle h, int64_t *nrecords, int64_t *ndropped, int
                       double *values_out, int reset) {
   if (!h) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_probe_read: NULL handle");
   tpsrhs_sampling_state *ss = h->sampling;
-  if (!ss || !ss->probe) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_probe_read: probes are not configured (tpsrhs_probe_configure)");
+  if (!ss || !ss->probe.sampler) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_probe_read: probes are not configured (tpsrhs_probe_configure)");
   return guarded([&] {
     HIP_CHECK(hipSetDevice(h->device));
-    const int64_t n = ss->nrecords, per = static_cast<int64_t>(h->neq) * ss->probe->npts;
-    if (times_out && n) HIP_CHECK(hipMemcpyAsync(times_out, ss->d_times, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-    if (values_out && n * per)
-      HIP_CHECK(hipMemcpyAsync(values_out, ss->d_values, sizeof(double) * n * per, hipMemcpyDeviceToHost, h->stream));
+    tpsrhs_probe_log &log = ss->probe;
+    fetch_rows(h, times_out, log.d_times, log.index.nrecords, 1);
+    fetch_rows(h, values_out, log.d_values, log.index.nrecords, static_cast<int64_t>(h->neq) * log.sampler->npts);
     HIP_CHECK(hipStreamSynchronize(h->stream));
-    if (nrecords) *nrecords = n;
-    if (ndropped) *ndropped = ss->ndropped;
-    if (iters_out && n) std::memcpy(iters_out, ss->iters.data(), sizeof(int64_t) * n);
-    if (reset) {  // the buffer starts again; the step counter goes on
-      ss->nrecords = ss->ndropped = 0;
-      ss->iters.clear();
-    }
+    read_index(log.index, nrecords, ndropped, iters_out, reset);
   });
 }
 
@@ -2110,20 +2051,14 @@ void launch_wall_distance(tpsrhs_operator *h, int64_t nfaces, const double *face
   if (grid >= (int64_t(1) << 31)) throw Unsupported("tpsrhs_wall_distance: more than 2^39 nodes");
   const char *env = std::getenv("TPSRHS_WALLDIST_CULL");
   const bool cull = !(env && env[0] == '0');
-  struct Table {
-    double *p = nullptr;
-    ~Table() {
-      if (p) (void)hipFree(p);
-    }
-  } table;
-  table.p = dev_upload(coef);
+  const DevBuf<double> table(coef);
   const dim3 g(static_cast<unsigned>(grid)), b(WD_BLOCK);
   if (cull)
     hipLaunchKernelGGL((k_wall_distance<DIM, true>), g, b, 0, h->stream, h->ndofs, h->order + 1, nodes, h->d_verts, nfaces,
-                       table.p, out);
+                       table.get(), out);
   else
     hipLaunchKernelGGL((k_wall_distance<DIM, false>), g, b, 0, h->stream, h->ndofs, h->order + 1, nodes, h->d_verts, nfaces,
-                       table.p, out);
+                       table.get(), out);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(h->stream));  // the table is freed on return
 }
@@ -2162,16 +2097,10 @@ int tpsrhs_wall_distance(tpsrhs_handle h, int64_t num_faces, const double *face_
 namespace {
 void monitor_off(tpsrhs_operator *h) {
   tpsrhs_integrals_state *is = h->integrals;
-  if (!is) return;
-  if (is->d_times) {  // (allocated first: set whenever any of the five is)
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);  // a record may still be running
-    for (double *p : {is->d_times, is->d_dts, is->d_totals, is->d_mins, is->d_maxs})
-      if (p) (void)hipFree(p);
-  }
-  is->d_times = is->d_dts = is->d_totals = is->d_mins = is->d_maxs = nullptr;
-  is->interval = is->capacity = is->count = is->nrecords = is->ndropped = 0;
-  is->iters.clear();
+  if (!is || !is->monitor.cadence.interval) return;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);  // a record may still be running
+  is->monitor = tpsrhs_monitor_log();
 }
 
 void integrals_release(tpsrhs_operator *h) {
@@ -2179,8 +2108,6 @@ void integrals_release(tpsrhs_operator *h) {
   if (!is) return;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);  // a reduction may still be running
-  monitor_off(h);
-  if (is->d_partial) (void)hipFree(is->d_partial);
   delete is;
   h->integrals = nullptr;
 }
@@ -2193,28 +2120,11 @@ void reduction_grid(int ne, int eb, int *blocks, int *run) {
   *blocks = std::max(1, (batches + per - 1) / per);
 }
 
-template <int DIM, int P>
-int integ_segments() {
-  return IntegCfg<DIM, P>::EB;
-}
-
 // the state with its scratch, sized once: the grids depend on the mesh and the order only
 tpsrhs_integrals_state *integrals_of(tpsrhs_operator *h) {
   if (h->integrals) return h->integrals;
   int eb = 0;
-  switch (h->dim * 10 + h->order) {
-    case 21: eb = integ_segments<2, 1>(); break;
-    case 22: eb = integ_segments<2, 2>(); break;
-    case 23: eb = integ_segments<2, 3>(); break;
-    case 24: eb = integ_segments<2, 4>(); break;
-    case 25: eb = integ_segments<2, 5>(); break;
-    case 31: eb = integ_segments<3, 1>(); break;
-    case 32: eb = integ_segments<3, 2>(); break;
-    case 33: eb = integ_segments<3, 3>(); break;
-    case 34: eb = integ_segments<3, 4>(); break;
-    case 35: eb = integ_segments<3, 5>(); break;
-    default: throw Unsupported("tpsrhs_integrate: dim 2 or 3 and polynomial orders 1..5 are built");
-  }
+  with_dim_order(h, "tpsrhs_integrate", [&](auto dim, auto p) { eb = IntegCfg<decltype(dim)::value, decltype(p)::value>::EB; });
   std::unique_ptr<tpsrhs_integrals_state> is(new tpsrhs_integrals_state());
   is->integ_eb = eb;
   reduction_grid(h->ne, eb, &is->integ_blocks, &is->integ_run);
@@ -2223,7 +2133,7 @@ tpsrhs_integrals_state *integrals_of(tpsrhs_operator *h) {
   reduction_grid(h->ne, 64 / is->stat_lpe, &is->stat_blocks, &is->stat_run);
   const int64_t per_row = std::max<int64_t>(2 * static_cast<int64_t>(is->integ_blocks) * eb,
                                              3 * static_cast<int64_t>(is->stat_blocks) * (64 / is->stat_lpe));
-  is->d_partial = dev_alloc<double>(INTEG_ROWS * per_row);
+  is->d_partial = DevBuf<double>(INTEG_ROWS * per_row);
   h->integrals = is.release();
   return h->integrals;
 }
@@ -2258,20 +2168,10 @@ void integrate_field(tpsrhs_operator *h, int nrows, const double *field, const d
   for (int r0 = 0; r0 < nrows; r0 += INTEG_ROWS) {  // the stream orders the launches: one scratch serves every slab of rows
     const int nr = std::min(INTEG_ROWS, nrows - r0);
     const double *f = field + r0 * h->ndofs, *ex = exact ? exact + r0 * npts : nullptr;
-    switch (h->dim * 10 + h->order) {
-      case 21: launch_integrate<2, 1>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
-      case 22: launch_integrate<2, 2>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
-      case 23: launch_integrate<2, 3>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
-      case 24: launch_integrate<2, 4>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
-      case 25: launch_integrate<2, 5>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
-      case 31: launch_integrate<3, 1>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
-      case 32: launch_integrate<3, 2>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
-      case 33: launch_integrate<3, 3>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
-      case 34: launch_integrate<3, 4>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
-      case 35: launch_integrate<3, 5>(h, is, tab, nr, f, ex, radial, is->d_partial); break;
-      default: throw Unsupported("tpsrhs_integrate: dim 2 or 3 and polynomial orders 1..5 are built");
-    }
-    hipLaunchKernelGGL(k_integrate_final<1024>, dim3(1), dim3(1024), 0, h->stream, nr, np, is->d_partial,
+    with_dim_order(h, "tpsrhs_integrate", [&](auto dim, auto p) {
+      launch_integrate<decltype(dim)::value, decltype(p)::value>(h, is, tab, nr, f, ex, radial, is->d_partial.get());
+    });
+    hipLaunchKernelGGL(k_integrate_final<1024>, dim3(1), dim3(1024), 0, h->stream, nr, np, is->d_partial.get(),
                        sum_out ? sum_out + r0 : nullptr, sumsq_out ? sumsq_out + r0 : nullptr);
     HIP_CHECK(hipGetLastError());
   }
@@ -2285,9 +2185,9 @@ void nodal_stats_field(tpsrhs_operator *h, int nrows, const double *field, doubl
     const int nr = std::min(INTEG_ROWS, nrows - r0);
     // (ne == 0: one block without elements writes the empty partials +inf, -inf, 0)
     hipLaunchKernelGGL(k_nodal_stats, dim3(is->stat_blocks, nr), dim3(64), 0, h->stream, h->ne, is->stat_run, npe, is->stat_lpe,
-                       h->ndofs, field + r0 * h->ndofs, is->d_partial);
+                       h->ndofs, field + r0 * h->ndofs, is->d_partial.get());
     HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_nodal_stats_final<1024>, dim3(1), dim3(1024), 0, h->stream, nr, np, h->ndofs, is->d_partial,
+    hipLaunchKernelGGL(k_nodal_stats_final<1024>, dim3(1), dim3(1024), 0, h->stream, nr, np, h->ndofs, is->d_partial.get(),
                        min_out ? min_out + r0 : nullptr, max_out ? max_out + r0 : nullptr,
                        meanabs_out ? meanabs_out + r0 : nullptr);
     HIP_CHECK(hipGetLastError());
@@ -2296,20 +2196,15 @@ void nodal_stats_field(tpsrhs_operator *h, int nrows, const double *field, doubl
 
 // One monitor record of the device vector x, stream-ordered, or one more dropped record when the buffer is full.
 void monitor_record(tpsrhs_operator *h, const double *x) {
-  tpsrhs_integrals_state *is = h->integrals;
-  if (is->nrecords >= is->capacity) {
-    is->ndropped++;
-    return;
-  }
-  const int64_t r = is->nrecords;
+  tpsrhs_monitor_log &log = h->integrals->monitor;
+  const int64_t r = log.index.claim(log.cadence.count);
+  if (r < 0) return;
   const int axisym = h->dim == 2 && h->nvel == 3;
-  integrate_field(h, h->neq, x, nullptr, axisym, is->d_totals + r * h->neq, nullptr);
-  nodal_stats_field(h, h->neq, x, is->d_mins + r * h->neq, is->d_maxs + r * h->neq, nullptr);
+  integrate_field(h, h->neq, x, nullptr, axisym, log.d_totals.get() + r * h->neq, nullptr);
+  nodal_stats_field(h, h->neq, x, log.d_mins.get() + r * h->neq, log.d_maxs.get() + r * h->neq, nullptr);
   // {dt of the next step, time}: the loop's control block, which the variable-dt loop never has on the host
-  HIP_CHECK(hipMemcpyAsync(is->d_dts + r, h->d_ctl, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  HIP_CHECK(hipMemcpyAsync(is->d_times + r, h->d_ctl + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  is->iters.push_back(is->count);
-  is->nrecords++;
+  HIP_CHECK(hipMemcpyAsync(log.d_dts.get() + r, h->d_ctl, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  HIP_CHECK(hipMemcpyAsync(log.d_times.get() + r, h->d_ctl + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
 }
 }  // namespace
 
@@ -2351,14 +2246,16 @@ int tpsrhs_monitor_configure(tpsrhs_handle h, int64_t interval, int64_t capacity
     if (interval == 0) return;
     HIP_CHECK(hipSetDevice(h->device));
     tpsrhs_integrals_state *is = integrals_of(h);  // with the scratch: a record allocates nothing
-    is->d_times = dev_alloc<double>(capacity);  // (first: monitor_off frees the others when this one is set)
-    is->d_dts = dev_alloc<double>(capacity);
-    is->d_totals = dev_alloc<double>(capacity * h->neq);
-    is->d_mins = dev_alloc<double>(capacity * h->neq);
-    is->d_maxs = dev_alloc<double>(capacity * h->neq);
+    tpsrhs_monitor_log log;
+    log.cadence.interval = interval;
+    log.index.capacity = capacity;
+    log.d_times = DevBuf<double>(capacity);
+    log.d_dts = DevBuf<double>(capacity);
+    log.d_totals = DevBuf<double>(capacity * h->neq);
+    log.d_mins = DevBuf<double>(capacity * h->neq);
+    log.d_maxs = DevBuf<double>(capacity * h->neq);
     if (!h->d_ctl) h->d_ctl = dev_alloc<double>(3);  // the loop's {dt, time, max speed}: a record copies from there
-    is->interval = interval;
-    is->capacity = capacity;
+    is->monitor = std::move(log);  // complete: a call that throws above leaves the monitor off
   });
 }
 
@@ -2366,27 +2263,19 @@ int tpsrhs_monitor_read(tpsrhs_handle h, int64_t *nrecords, int64_t *ndropped, i
                         double *dts_out, double *totals_out, double *mins_out, double *maxs_out, int reset) {
   if (!h) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_monitor_read: NULL handle");
   tpsrhs_integrals_state *is = h->integrals;
-  if (!is || !is->interval)
+  if (!is || !is->monitor.cadence.interval)
     return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_monitor_read: the monitor is not configured (tpsrhs_monitor_configure)");
   return guarded([&] {
     HIP_CHECK(hipSetDevice(h->device));
-    const int64_t n = is->nrecords;
-    auto fetch = [&](double *dst, const double *src, int64_t count) {
-      if (dst && count) HIP_CHECK(hipMemcpyAsync(dst, src, sizeof(double) * count, hipMemcpyDeviceToHost, h->stream));
-    };
-    fetch(times_out, is->d_times, n);
-    fetch(dts_out, is->d_dts, n);
-    fetch(totals_out, is->d_totals, n * h->neq);
-    fetch(mins_out, is->d_mins, n * h->neq);
-    fetch(maxs_out, is->d_maxs, n * h->neq);
+    tpsrhs_monitor_log &log = is->monitor;
+    const int64_t n = log.index.nrecords;
+    fetch_rows(h, times_out, log.d_times, n, 1);
+    fetch_rows(h, dts_out, log.d_dts, n, 1);
+    fetch_rows(h, totals_out, log.d_totals, n, h->neq);
+    fetch_rows(h, mins_out, log.d_mins, n, h->neq);
+    fetch_rows(h, maxs_out, log.d_maxs, n, h->neq);
     HIP_CHECK(hipStreamSynchronize(h->stream));
-    if (nrecords) *nrecords = n;
-    if (ndropped) *ndropped = is->ndropped;
-    if (iters_out && n) std::memcpy(iters_out, is->iters.data(), sizeof(int64_t) * n);
-    if (reset) {  // the buffer starts again; the step counter goes on
-      is->nrecords = is->ndropped = 0;
-      is->iters.clear();
-    }
+    read_index(log.index, nrecords, ndropped, iters_out, reset);
   });
 }
 
