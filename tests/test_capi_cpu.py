@@ -98,6 +98,46 @@ def test_unsupported_configurations_are_refused():
         capi.face_tables(c.mesh, c.bcs[:2])
 
 
+def _create_status(mesh, disc, physics, bcs=()):
+    lib = capi.load()
+    ma = capi.MeshArgs(mesh)
+    arr = (capi.BC * max(len(bcs), 1))(*bcs)
+    h = C.c_void_p()
+    st = lib.tpsrhs_create(C.byref(ma.c), C.byref(disc), C.byref(physics), len(bcs), arr, None, C.byref(h))
+    assert not h.value
+    return st, lib.tpsrhs_last_error().decode()
+
+
+def test_les_and_sponge_refusals_need_no_device():
+    """the refusals of tests/test_gpu_les.py::test_unsupported_combinations, through tpsrhs_create itself: they come from the
+    plan (operator_plan.hpp), ahead of the device probe, with their own status on a machine without a GPU as well"""
+    ph = capi.dry_air_physics(capi.NS)
+    ph.sgs.model_type = capi.SGS_SMAGORINSKY
+    st, msg = _create_status(meshgen.box_quad(3, 3), capi.Disc(2, 0, 0, 0, 0), ph)
+    assert st == 2 and "dim == 3" in msg
+    st, msg = _create_status(meshgen.box_hex(3, 3, 3), capi.Disc(2, 1, 1, 0, 0), ph)
+    assert st == 2 and "Gauss-Legendre" in msg
+    pl = capi.argon_ternary_physics()
+    pl.visc_sponge.enabled, pl.visc_sponge.width = 1, 1.0
+    st, msg = _create_status(meshgen.box_hex(3, 3, 3), capi.Disc(2, 0, 0, 0, 0), pl)
+    assert st == 2 and "planar 2-D and the axisymmetric" in msg
+
+
+def test_lte_refusals_need_no_device():
+    """the refusals of tests/test_lte.py::test_lte_unsupported, through tpsrhs_create itself"""
+    st, msg = _create_status(meshgen.box_hex(3, 3, 3), capi.Disc(2, 0, 0, 0, 0), capi.lte_physics())
+    assert st == 2 and "axisymmetric" in msg
+    c = cases.lte_axisym(3, 3, 2)
+    c.physics.sgs.model_type = capi.SGS_SMAGORINSKY
+    st, msg = _create_status(c.mesh, c.disc, c.physics, c.bcs)
+    assert st == 2 and "3-D" in msg
+    pl = capi.argon_ternary_physics()
+    pl.visc_sponge.enabled, pl.visc_sponge.width = 1, 1.0
+    pl.visc_sponge.normal[0] = 1.0
+    st, msg = _create_status(meshgen.box_hex(3, 3, 3), capi.Disc(2, 0, 0, 0, 0), pl)
+    assert st == 2 and "planar 2-D and the axisymmetric" in msg
+
+
 @pytest.mark.parametrize("dim", [2, 3])
 def test_face_tables_match_geometry(dim):
     """neighbour slots are mutual and the orientation code maps my face points onto the

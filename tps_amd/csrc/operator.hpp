@@ -16,53 +16,14 @@
 
 #include "../../include/tpsrhs.h"
 #include "basis.hpp"
+#include "device_buffer.hpp"
 #include "kernels.hpp"
 #include "topology.hpp"
+#include "unsupported.hpp"
 
 using namespace tpsrhs;
 
 namespace {
-
-struct DeviceError : std::runtime_error {
-  explicit DeviceError(const std::string &s) : std::runtime_error(s) {}
-};
-struct Unsupported : std::runtime_error {
-  explicit Unsupported(const std::string &s) : std::runtime_error(s) {}
-};
-
-#define HIP_CHECK(expr)                                                                                   \
-  do {                                                                                                    \
-    hipError_t _e = (expr);                                                                               \
-    if (_e != hipSuccess)                                                                                 \
-      throw DeviceError(std::string(#expr) + ": " + hipGetErrorString(_e) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"); \
-  } while (0)
-
-// TPSRHS_POISON=1 (debug / tests/test_gpu_poison.py): every device allocation of the library starts as all-ones bytes
-// (a NaN as a double, -1 as an index), so that a read of memory no kernel has written shows up as a NaN in the
-// residual instead of depending on what the allocator happened to return.  Read at every call: cheap next to hipMalloc.
-inline bool poison_allocations() {
-  const char *e = std::getenv("TPSRHS_POISON");
-  return e && e[0] == '1';
-}
-template <class T>
-T *dev_alloc(size_t n) {
-  T *p = nullptr;
-  const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-  HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&p), bytes));
-  if (poison_allocations()) {
-    HIP_CHECK(hipMemset(p, 0xFF, bytes));
-    // the fill runs on the NULL stream, which is not ordered against a non-blocking stream (torch's side streams): it
-    // must be complete before the operator's stream first writes p (else a freshly zeroed NaN counter reads -1)
-    HIP_CHECK(hipDeviceSynchronize());
-  }
-  return p;
-}
-template <class T>
-T *dev_upload(const std::vector<T> &v) {
-  T *p = dev_alloc<T>(v.size());
-  if (!v.empty()) HIP_CHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return p;
-}
 
 constexpr int NKERN = 3;
 const char *kKernelNames[NKERN] = {"k_traces", "k_gradient", "k_flux"};
@@ -76,7 +37,7 @@ struct tpsrhs_integrals_state;  // integrals.hpp: reduction scratch and monitor 
 struct tpsrhs_operator {
   int dim = 0, order = 0, neq = 0, nvel = 0;
   int nc = 0;  // 1: the non-collocated Gauss-Lobatto pair (basisType 1, integrationRule 1), 0: the collocated Gauss-Legendre pair
-  double *d_minv = nullptr;  // nc: [ne][npe][npe] inverse element mass matrices
+  DevBuf<double> d_minv;  // nc: [ne][npe][npe] inverse element mass matrices
   int ne = 0, nfaces = 0, nf = 0, nq = 0;
   int64_t ndofs = 0;
   int device = 0;
@@ -84,36 +45,36 @@ struct tpsrhs_operator {
   Topology topo;
   tpsrhs_physics phys;
   alignas(16) unsigned char params[4096];  // PH::Params of the selected physics, passed by value
-  void *d_chem = nullptr;                   // ChemDev block + table storage (plasma)
-  void *d_params = nullptr;                 // device image of `params` for the physics that read it through a pointer (plasma)
-  std::vector<void *> d_extra;
-  std::vector<void *> d_mixed_out;  // plane-node lists / sum buffers of the current forcing's mixed-out sponge zones
-  // device data
-  double *d_verts = nullptr;
-  int2 *d_face_info = nullptr;
-  double *d_Up = nullptr, *d_gradUp = nullptr, *d_TA = nullptr, *d_TB = nullptr;
-  double *d_speed = nullptr, *d_block_speed = nullptr;
+  // device data: every buffer has its owner here (device_buffer.hpp), also those created at their first use
+  DevBuf<void> d_chem;                // ChemDev block (plasma)
+  DevBuf<void> d_params;              // device image of `params` for the physics that read it through a pointer (plasma)
+  std::vector<DevBuf<void>> d_extra;  // what the parameter block points to: table coefficients, search aids, element sizes
+  std::vector<DevBuf<void>> d_mixed_out;  // plane-node lists / sum buffers of the current forcing's mixed-out sponge zones
+  DevBuf<double> d_verts;
+  DevBuf<int2> d_face_info;
+  DevBuf<double> d_Up, d_gradUp, d_TA, d_TB;
+  DevBuf<double> d_speed, d_block_speed;
   int flux_grid = 0;
-  double *d_xh = nullptr, *d_yh = nullptr;  // staging for tpsrhs_mult_host
-  double *d_rk = nullptr;                   // k | y | z of tpsrhs_rk4_step
-  unsigned long long *d_nan = nullptr;
+  DevBuf<double> d_xh, d_yh;  // staging for tpsrhs_mult_host
+  DevBuf<double> d_rk;        // k | y | z of tpsrhs_rk4_step
+  DevBuf<unsigned long long> d_nan;
   RkDev rk = {};  // mode 0 outside tpsrhs_rk4_step / tpsrhs_advance: k_flux writes the residual
   MixLenDev mixlen = {nullptr, 0.0, 1.0, 0.0};  // MixingLengthTransport (tpsrhs_set_mixing_length); distance NULL: off
   ForcingDev forcing = {};                  // host copy of the optional forcing terms (tpsrhs_set_forcing / _joule_heating)
-  ForcingDev *d_forcing = nullptr;
+  DevBuf<ForcingDev> d_forcing;
   bool forcing_active = false;
   // non-reflecting inlet / outlet patches (dry air): their faces {slot, bc index}, slot -> ordinal, the
   // double-buffered boundary state, the patch sums of the primitives, the time step they integrate with
   bool has_nr = false;  // some boundary condition is of a non-reflecting type (possibly without local faces)
   int n_nr_faces = 0;
-  int2 *d_nr_faces = nullptr;
-  int *d_nr_ordinal = nullptr;
-  double *d_bstate[2] = {nullptr, nullptr};
+  DevBuf<int2> d_nr_faces;
+  DevBuf<int> d_nr_ordinal;
+  DevBuf<double> d_bstate[2];
   int bstate_cur = 0;
   bool bstate_init = false;
-  double *d_bc_sums = nullptr;
+  DevBuf<double> d_bc_sums;
   double nr_dt = 0.0;
-  double *d_ctl = nullptr;          // {dt, time, max speed} of tpsrhs_advance
+  DevBuf<double> d_ctl;             // {dt, time, max speed} of tpsrhs_advance
   const double *nr_dt_dev = nullptr;  // non-NULL while tpsrhs_advance runs: the boundary conditions read dt there
   tpsrhs_reduce_fn reduce = nullptr;
   void *reduce_ctx = nullptr;
@@ -136,11 +97,11 @@ struct tpsrhs_operator {
   void *halo_ctx = nullptr;
   hipStream_t comm_stream = nullptr;  // second stream: pack + exchange overlap the interior blocks
   hipEvent_t ev_halo[4] = {};         // traces of the halo blocks ready / TA received / TB ready / TB received
-  int *d_blocks_halo = nullptr, *d_blocks_interior = nullptr;
+  DevBuf<int> d_blocks_halo, d_blocks_interior;
   int n_blocks_halo = 0, n_blocks_interior = 0;
-  int32_t *d_shared_slot = nullptr;
-  uint8_t *d_shared_orient = nullptr;
-  double *d_send = nullptr;
+  DevBuf<int32_t> d_shared_slot;
+  DevBuf<uint8_t> d_shared_orient;
+  DevBuf<double> d_send;
   std::vector<int64_t> send_off[2], recv_off[2];
   // timing
   // per-kernel timing: a ring of event sets so that a timed loop never synchronises
@@ -158,21 +119,19 @@ struct tpsrhs_operator {
   bool fuse_traces = true;
   bool ta_valid = false;     // d_ta_next holds the traces of the input of the stage that runs next
   bool ta_chain = false;     // inside tpsrhs_advance: stage 4 leaves the traces of the new solution for the next step
-  double *d_TA2 = nullptr, *d_ta_next = nullptr;
+  DevBuf<double> d_TA2;
+  double *d_ta_next = nullptr;  // d_TA or d_TA2
   bool sweep_alt = true;  // alternate the direction of consecutive sweeps (launch_all); TPSRHS_SWEEP_ALT
   int sweep_parity = 0;
   VsDev vs2d = {};  // viscous sponge of the 2-D heavy kernels (MeshDev::vs); enabled = 0: none
-  // tpsrhs_stats_configure; NULL: no statistics.  Owned by tpsrhs.hip (created, used and freed there: the kernel families
-  // never touch it).  Last member: nothing before it moves.
+  // tpsrhs_stats_configure / tpsrhs_sampler_create, tpsrhs_probe_configure / tpsrhs_integrate, tpsrhs_monitor_configure;
+  // NULL: none yet.  Created, used and released (tpsrhs_destroy) by tpsrhs.hip.  Raw pointers because their types are
+  // incomplete in the kernel families, where this struct's inline destructor is compiled as well.
   tpsrhs_stats_state *stats = nullptr;
-  // tpsrhs_sampler_create / tpsrhs_probe_configure; NULL: none yet.  The host copy of the element vertices, the samplers
-  // this operator owns and the probe buffer; owned by tpsrhs.hip like `stats`, and appended after it for the same reason.
   tpsrhs_sampling_state *sampling = nullptr;
-  // tpsrhs_integrate / tpsrhs_nodal_stats / tpsrhs_monitor_configure; NULL: none yet.  The reduction scratch and the monitor
-  // records; owned by tpsrhs.hip like `stats` and `sampling`, and appended after them for the same reason.
   tpsrhs_integrals_state *integrals = nullptr;
   // tpsrhs_visualization_fields: the post-processing passes of the plasma families (visualization.hpp); NULL for every other
-  // physics.  Appended after `integrals` for the same reason: the kernel families see the members above where they were.
+  // physics
   void (*vis_fields)(tpsrhs_operator *, const VisRows &, const double *, double *) = nullptr;
 
   MeshDev mesh_dev() const {
@@ -181,39 +140,20 @@ struct tpsrhs_operator {
     m.ne = ne;
     m.reverse = 0;
     m.ndofs = ndofs;
-    m.verts = d_verts;
-    m.face_info = d_face_info;
-    m.minv = d_minv;
+    m.verts = d_verts.get();
+    m.face_info = d_face_info.get();
+    m.minv = d_minv.get();
     m.ml = mixlen;
     m.vs = vs2d;
     return m;
   }
+  // what is not memory; the buffers free themselves after this body, on the device set here
   ~tpsrhs_operator() {
     (void)hipSetDevice(device);
-    for (void *p : {static_cast<void *>(d_verts), static_cast<void *>(d_face_info),
-                    static_cast<void *>(d_Up), static_cast<void *>(d_gradUp),
-                    static_cast<void *>(d_TA), static_cast<void *>(d_TB), static_cast<void *>(d_speed), static_cast<void *>(d_block_speed),
-                    static_cast<void *>(d_xh), static_cast<void *>(d_yh), static_cast<void *>(d_shared_slot),
-                    static_cast<void *>(d_shared_orient), static_cast<void *>(d_send)})
-      if (p) (void)hipFree(p);
-    if (d_chem) (void)hipFree(d_chem);
-    if (d_params) (void)hipFree(d_params);
-    if (d_minv) (void)hipFree(d_minv);
-    if (d_TA2) (void)hipFree(d_TA2);
-    if (d_rk) (void)hipFree(d_rk);
-    if (d_nan) (void)hipFree(d_nan);
-    if (d_forcing) (void)hipFree(d_forcing);
     if (step_graph) (void)hipGraphExecDestroy(step_graph);
-    for (void *p : {static_cast<void *>(d_nr_faces), static_cast<void *>(d_nr_ordinal), static_cast<void *>(d_bstate[0]),
-                    static_cast<void *>(d_bstate[1]), static_cast<void *>(d_bc_sums), static_cast<void *>(d_ctl)})
-      if (p) (void)hipFree(p);
-    if (d_blocks_halo) (void)hipFree(d_blocks_halo);
-    if (d_blocks_interior) (void)hipFree(d_blocks_interior);
     for (auto &e : ev_halo)
       if (e) (void)hipEventDestroy(e);
     if (comm_stream) (void)hipStreamDestroy(comm_stream);
-    for (void *p : d_extra) (void)hipFree(p);
-    for (void *p : d_mixed_out) (void)hipFree(p);
     for (auto &set : evs)
       for (auto &e : set)
         if (e) (void)hipEventDestroy(e);
@@ -229,10 +169,10 @@ template <class PH>
 typename PH::KArg kernel_params(tpsrhs_operator *op) {
   if constexpr (std::is_pointer<typename PH::KArg>::value) {
     if (!op->d_params) {
-      op->d_params = dev_alloc<unsigned char>(sizeof(op->params));
-      HIP_CHECK(hipMemcpy(op->d_params, op->params, sizeof(op->params), hipMemcpyHostToDevice));
+      op->d_params = DevBuf<unsigned char>(sizeof(op->params));
+      HIP_CHECK(hipMemcpy(op->d_params.get(), op->params, sizeof(op->params), hipMemcpyHostToDevice));
     }
-    return reinterpret_cast<typename PH::KArg>(op->d_params);
+    return reinterpret_cast<typename PH::KArg>(op->d_params.get());
   } else {
     return *reinterpret_cast<const typename PH::Params *>(op->params);
   }
@@ -245,14 +185,14 @@ inline void exchange(tpsrhs_operator *op, int phase, double *T, int nfld, int pe
   const int64_t total = static_cast<int64_t>(tp.num_shared) * nfld * per;
   const int grid = static_cast<int>(std::min<int64_t>((total + 255) / 256, 2048));
   if (op->dim == 3)
-    hipLaunchKernelGGL(k_pack<3>, dim3(grid), dim3(256), 0, stream, tp.num_shared, nfld, n1, op->d_shared_slot,
-                       op->d_shared_orient, T, op->d_send);
+    hipLaunchKernelGGL(k_pack<3>, dim3(grid), dim3(256), 0, stream, tp.num_shared, nfld, n1, op->d_shared_slot.get(),
+                       op->d_shared_orient.get(), T, op->d_send.get());
   else
-    hipLaunchKernelGGL(k_pack<2>, dim3(grid), dim3(256), 0, stream, tp.num_shared, nfld, n1, op->d_shared_slot,
-                       op->d_shared_orient, T, op->d_send);
+    hipLaunchKernelGGL(k_pack<2>, dim3(grid), dim3(256), 0, stream, tp.num_shared, nfld, n1, op->d_shared_slot.get(),
+                       op->d_shared_orient.get(), T, op->d_send.get());
   HIP_CHECK(hipGetLastError());
   double *recv = T + static_cast<int64_t>(op->ne) * op->nfaces * nfld * per;
-  const int st = op->halo(op->halo_ctx, phase, op->d_send, recv, static_cast<int>(tp.nbr_ranks.size()),
+  const int st = op->halo(op->halo_ctx, phase, op->d_send.get(), recv, static_cast<int>(tp.nbr_ranks.size()),
                           tp.nbr_ranks.data(), op->send_off[phase].data(), op->recv_off[phase].data(), stream);
   if (st != 0) throw std::runtime_error("halo callback failed in phase " + std::to_string(phase));
 }
@@ -266,13 +206,13 @@ void launch_all(tpsrhs_operator *op, const double *x, double *y, bool gradients_
   hipStream_t s = op->stream;
   if constexpr (PH::HAS_NR_BC) {  // this Mult's view of the non-reflecting boundary state
     typename PH::Params &w = *reinterpret_cast<typename PH::Params *>(op->params);
-    w.bstate = op->d_bstate[op->bstate_cur];
-    w.nr_ordinal = op->d_nr_ordinal;
+    w.bstate = op->d_bstate[op->bstate_cur].get();
+    w.nr_ordinal = op->d_nr_ordinal.get();
     w.nr_dt = op->nr_dt;
   }
   const typename PH::KArg prm_k = kernel_params<PH>(op);  // after the update above: what the kernels of this Mult get
   if (!op->d_block_speed && !gradients_only) {
-    op->d_block_speed = dev_alloc<double>(nblocks);
+    op->d_block_speed = DevBuf<double>(nblocks);
     op->flux_grid = nblocks;
   }
   // Alternating sweep direction (TPSRHS_SWEEP_ALT): k_traces and k_flux of a Mult walk the block list one way, k_gradient
@@ -280,7 +220,7 @@ void launch_all(tpsrhs_operator *op, const double *x, double *y, bool gradients_
   // (xcd_block).  The direction is per sweep, the same for its halo and interior launches.
   const int dir0 = op->sweep_alt ? op->sweep_parity : 0;
   // which trace buffer this Mult reads, whether its k_traces sweep is already done, and where k_flux puts the next one's
-  double *ta = op->d_TA;
+  double *ta = op->d_TA.get();
   bool have_traces = false;
   if constexpr (flux_fuses_traces<C, PH>()) {
     const int stage = op->rk.mode;
@@ -292,8 +232,8 @@ void launch_all(tpsrhs_operator *op, const double *x, double *y, bool gradients_
     }
     op->ta_valid = false;
     if (op->fuse_traces && !gradients_only && op->topo.num_shared == 0 && stage >= 1 && (stage <= 3 || op->ta_chain)) {
-      if (!op->d_TA2) op->d_TA2 = dev_alloc<double>(static_cast<int64_t>(op->ne) * op->nfaces * 2 * PH::NEQ * C::NF);
-      op->rk.ta_out = (ta == op->d_TA) ? op->d_TA2 : op->d_TA;
+      if (!op->d_TA2) op->d_TA2 = DevBuf<double>(static_cast<int64_t>(op->ne) * op->nfaces * 2 * PH::NEQ * C::NF);
+      op->rk.ta_out = (ta == op->d_TA.get()) ? op->d_TA2.get() : op->d_TA.get();
       op->d_ta_next = op->rk.ta_out;
       op->ta_valid = true;  // (cleared again below if a launch throws)
     }
@@ -308,14 +248,14 @@ void launch_all(tpsrhs_operator *op, const double *x, double *y, bool gradients_
   };
   auto gradient = [&](MeshDev m, int grid) {
     m.reverse = op->sweep_alt ? 1 - dir0 : 0;
-    hipLaunchKernelGGL((k_gradient<C, PH>), dim3(grid), dim3(C::BLOCK), 0, s, m, prm_k, x, ta, op->d_Up, op->d_gradUp,
-                       op->d_TB);
+    hipLaunchKernelGGL((k_gradient<C, PH>), dim3(grid), dim3(C::BLOCK), 0, s, m, prm_k, x, ta, op->d_Up.get(), op->d_gradUp.get(),
+                       op->d_TB.get());
     HIP_CHECK(hipGetLastError());
   };
   auto flux = [&](MeshDev m, int grid) {
     m.reverse = dir0;
-    hipLaunchKernelGGL((k_flux<C, PH>), dim3(grid), dim3(C::BLOCK), 0, s, m, prm_k, x, op->d_gradUp, ta, op->d_TB, y,
-                       op->d_block_speed, op->rk);
+    hipLaunchKernelGGL((k_flux<C, PH>), dim3(grid), dim3(C::BLOCK), 0, s, m, prm_k, x, op->d_gradUp.get(), ta, op->d_TB.get(), y,
+                       op->d_block_speed.get(), op->rk);
     HIP_CHECK(hipGetLastError());
   };
   // non-reflecting patches: mean of the primitives (+ sum over the ranks), then the boundary-state update;
@@ -324,16 +264,16 @@ void launch_all(tpsrhs_operator *op, const double *x, double *y, bool gradients_
     if constexpr (PH::HAS_NR_BC) {
       if (!op->has_nr) return;
       const int nbc = prm.num_bcs;
-      hipLaunchKernelGGL((k_bc_mean<C, PH>), dim3(nbc), dim3(256), 0, s, op->n_nr_faces, op->d_nr_faces, ta,
-                         op->d_bc_sums);
+      hipLaunchKernelGGL((k_bc_mean<C, PH>), dim3(nbc), dim3(256), 0, s, op->n_nr_faces, op->d_nr_faces.get(), ta,
+                         op->d_bc_sums.get());
       HIP_CHECK(hipGetLastError());
       if (op->reduce && op->topo.num_shared > 0) {
-        const int st = op->reduce(op->reduce_ctx, op->d_bc_sums, nbc * (TPSRHS_MAXEQUATIONS + 1), TPSRHS_REDUCE_SUM, s);
+        const int st = op->reduce(op->reduce_ctx, op->d_bc_sums.get(), nbc * (TPSRHS_MAXEQUATIONS + 1), TPSRHS_REDUCE_SUM, s);
         if (st != 0) throw std::runtime_error("halo: reduce callback failed");
       }
       if (op->n_nr_faces > 0) {
-        hipLaunchKernelGGL((k_bc_nr<C, PH>), dim3(op->n_nr_faces), dim3(C::BLOCK), 0, s, m, prm_k, op->d_nr_faces, op->d_bc_sums, x,
-                           op->d_Up, op->d_gradUp, op->d_bstate[op->bstate_cur], op->d_bstate[1 - op->bstate_cur],
+        hipLaunchKernelGGL((k_bc_nr<C, PH>), dim3(op->n_nr_faces), dim3(C::BLOCK), 0, s, m, prm_k, op->d_nr_faces.get(), op->d_bc_sums.get(), x,
+                           op->d_Up.get(), op->d_gradUp.get(), op->d_bstate[op->bstate_cur].get(), op->d_bstate[1 - op->bstate_cur].get(),
                            op->bstate_init ? 0 : 1, op->nr_dt_dev);
         HIP_CHECK(hipGetLastError());
       }
@@ -345,18 +285,18 @@ void launch_all(tpsrhs_operator *op, const double *x, double *y, bool gradients_
     if constexpr (PH::HAS_MIXED_OUT) {  // SpongeZone::updateTerms: computeMixedOutValues first (src/forcing_terms.cpp:631-635)
       for (int z = 0; z < op->forcing.nsponge; z++) {
         if (!op->forcing.sponge[z].mixed_out) continue;
-        hipLaunchKernelGGL((k_mixed_out_sum<C, PH>), dim3(1), dim3(256), 0, s, op->ndofs, prm_k, op->d_forcing, z, x);
+        hipLaunchKernelGGL((k_mixed_out_sum<C, PH>), dim3(1), dim3(256), 0, s, op->ndofs, prm_k, op->d_forcing.get(), z, x);
         HIP_CHECK(hipGetLastError());
         if (op->reduce && op->topo.num_shared > 0) {  // MPI_Allreduce of meanNormalFluxes, :732-735
           const int st = op->reduce(op->reduce_ctx, op->forcing.sponge[z].msum, PH::NEQ + 1, TPSRHS_REDUCE_SUM, s);
           if (st != 0) throw std::runtime_error("mixed-out sponge: reduce callback failed");
         }
-        hipLaunchKernelGGL((k_mixed_out_finish<C, PH>), dim3(1), dim3(1), 0, s, prm_k, op->d_forcing, z);
+        hipLaunchKernelGGL((k_mixed_out_finish<C, PH>), dim3(1), dim3(1), 0, s, prm_k, op->d_forcing.get(), z);
         HIP_CHECK(hipGetLastError());
       }
     }
     const int grid = static_cast<int>((op->ndofs + 255) / 256);
-    hipLaunchKernelGGL((k_forcing<C, PH>), dim3(grid), dim3(256), 0, s, m, prm_k, op->d_forcing, x, op->d_gradUp, y);
+    hipLaunchKernelGGL((k_forcing<C, PH>), dim3(grid), dim3(256), 0, s, m, prm_k, op->d_forcing.get(), x, op->d_gradUp.get(), y);
     HIP_CHECK(hipGetLastError());
   };
   if (op->timing) {
@@ -385,14 +325,14 @@ void launch_all(tpsrhs_operator *op, const double *x, double *y, bool gradients_
       for (int b = 0; b < nblocks; b++) (is_halo[b] ? halo : interior).push_back(b);
       op->n_blocks_halo = static_cast<int>(halo.size());
       op->n_blocks_interior = static_cast<int>(interior.size());
-      op->d_blocks_halo = dev_upload(halo);
-      op->d_blocks_interior = dev_upload(interior);
+      op->d_blocks_halo = DevBuf<int>(halo);
+      op->d_blocks_interior = DevBuf<int>(interior);
       HIP_CHECK(hipStreamCreateWithFlags(&op->comm_stream, hipStreamNonBlocking));
       for (auto &e : op->ev_halo) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     MeshDev mh = all, mi = all;
-    mh.blocks = op->d_blocks_halo;
-    mi.blocks = op->d_blocks_interior;
+    mh.blocks = op->d_blocks_halo.get();
+    mi.blocks = op->d_blocks_interior.get();
     const int nh = op->n_blocks_halo, ni = op->n_blocks_interior;
     hipStream_t c = op->comm_stream;
     // host order: the interior launches are enqueued BEFORE the (host-side, slow) exchange callback, so
@@ -403,7 +343,7 @@ void launch_all(tpsrhs_operator *op, const double *x, double *y, bool gradients_
     if (op->timing) HIP_CHECK(hipEventRecord(op->ev[1], s));
     if (ni) gradient(mi, ni);
     HIP_CHECK(hipStreamWaitEvent(c, op->ev_halo[0], 0));
-    exchange(op, 0, op->d_TA, 2 * PH::NEQ, C::NF, c);  // overlaps the two interior launches above
+    exchange(op, 0, op->d_TA.get(), 2 * PH::NEQ, C::NF, c);  // overlaps the two interior launches above
     HIP_CHECK(hipEventRecord(op->ev_halo[1], c));
     HIP_CHECK(hipStreamWaitEvent(s, op->ev_halo[1], 0));
     gradient(mh, nh);
@@ -413,7 +353,7 @@ void launch_all(tpsrhs_operator *op, const double *x, double *y, bool gradients_
     nr_update(all);
     if (ni) flux(mi, ni);
     HIP_CHECK(hipStreamWaitEvent(c, op->ev_halo[2], 0));
-    exchange(op, 1, op->d_TB, PH::NEQ - 1, C::NQ, c);  // overlaps the interior flux launch
+    exchange(op, 1, op->d_TB.get(), PH::NEQ - 1, C::NQ, c);  // overlaps the interior flux launch
     HIP_CHECK(hipEventRecord(op->ev_halo[3], c));
     HIP_CHECK(hipStreamWaitEvent(s, op->ev_halo[3], 0));
     flux(mh, nh);
@@ -497,13 +437,13 @@ void launch_vis_fields(tpsrhs_operator *op, const VisRows &rows, const double *x
   const int grid = static_cast<int>((n + 255) / 256);
   if (grid == 0) return;
   const typename PH::KArg prm_k = kernel_params<PH>(op);
-  hipLaunchKernelGGL((k_vis_fields<PH, VIS_SPECIES>), dim3(grid), dim3(256), 0, op->stream, prm_k, rows, n, x, op->d_Up, op->d_gradUp, out);
+  hipLaunchKernelGGL((k_vis_fields<PH, VIS_SPECIES>), dim3(grid), dim3(256), 0, op->stream, prm_k, rows, n, x, op->d_Up.get(), op->d_gradUp.get(), out);
   HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL((k_vis_fields<PH, VIS_FLUX>), dim3(grid), dim3(256), 0, op->stream, prm_k, rows, n, x, op->d_Up, op->d_gradUp, out);
+  hipLaunchKernelGGL((k_vis_fields<PH, VIS_FLUX>), dim3(grid), dim3(256), 0, op->stream, prm_k, rows, n, x, op->d_Up.get(), op->d_gradUp.get(), out);
   HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL((k_vis_fields<PH, VIS_SIGMA>), dim3(grid), dim3(256), 0, op->stream, prm_k, rows, n, x, op->d_Up, op->d_gradUp, out);
+  hipLaunchKernelGGL((k_vis_fields<PH, VIS_SIGMA>), dim3(grid), dim3(256), 0, op->stream, prm_k, rows, n, x, op->d_Up.get(), op->d_gradUp.get(), out);
   HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL((k_vis_fields<PH, VIS_SOURCE>), dim3(grid), dim3(256), 0, op->stream, prm_k, rows, n, x, op->d_Up, op->d_gradUp, out);
+  hipLaunchKernelGGL((k_vis_fields<PH, VIS_SOURCE>), dim3(grid), dim3(256), 0, op->stream, prm_k, rows, n, x, op->d_Up.get(), op->d_gradUp.get(), out);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -84,7 +84,9 @@ extern "C" int tpsrhs_debug_dumpf(double *out, int n) {
 
 // One family = one shared object, libtpsrhs_<unit>.so, that the core library loads on demand (tpsrhs.hip::load_family).
 // The entry point is C: no exception crosses the boundary, a refusal comes back as a status code and a message.
+// <name>_operator_size is the layout of tpsrhs_operator this unit was compiled against: the loader refuses another.
 #define TPSRHS_PLASMA_FAMILY(name, DIM, NVEL, NSP, AMBI)                                                              \
+  extern "C" { unsigned long name##_operator_size = sizeof(tpsrhs_operator); }                                        \
   extern "C" int name(tpsrhs_operator *op, int two_temperature, int transport, char *err, int errlen) {               \
     auto say = [&](const char *what) {                                                                                \
       if (err && errlen > 0) {                                                                                        \

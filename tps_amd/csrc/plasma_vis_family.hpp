@@ -48,8 +48,10 @@ static void pick_plasma_vis(tpsrhs_operator *op, bool two_temperature, int trans
   }
 }
 
-// The entry point is C, with the signature of the sweeps' families: no exception crosses the boundary.
+// The entry point is C, with the signature of the sweeps' families (and their <name>_operator_size): no exception crosses
+// the boundary.
 #define TPSRHS_PLASMA_VIS_FAMILY(name, DIM, NVEL, NSP, AMBI)                                                          \
+  extern "C" { unsigned long name##_operator_size = sizeof(tpsrhs_operator); }                                        \
   extern "C" int name(tpsrhs_operator *op, int two_temperature, int transport, char *err, int errlen) {               \
     try {                                                                                                             \
       pick_plasma_vis<DIM, NVEL, NSP, AMBI>(op, two_temperature != 0, transport);                                     \

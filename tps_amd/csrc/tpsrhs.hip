@@ -4,9 +4,10 @@
 // HBM, and enqueues the three sweeps of kernels.hpp on one HIP stream per operator.  There is no
 // CPU fallback: without a HIP device tpsrhs_create returns TPSRHS_ERR_NO_DEVICE.
 #include "operator.hpp"
-#include "device_buffer.hpp"
+#include "element_geometry.hpp"
 #include "integrals.hpp"
 #include "locate_device.hpp"
+#include "operator_plan.hpp"
 #include "physics_dryair.hpp"
 #include "physics_dryair_axisym.hpp"
 #include "physics_plasma.hpp"
@@ -42,7 +43,8 @@ namespace {
 // libtpsrhs_plasma_<geo>_n<species>[a][_hi].so in the directory of this library, or in a directory of the colon-separated
 // TPSRHS_FAMILY_PATH (development: A/B builds of one family).  dlopen'ed at the first operator that needs it and kept
 // for the life of the process (the operator holds pointers to its launch functions).  The entry point is C and
-// returns a status: no exception crosses the boundary.  A missing family is a loud error, never another code path.
+// returns a status: no exception crosses the boundary.  A missing family is a loud error, never another code path, and so is
+// one that was compiled against another layout of tpsrhs_operator (it exports the size it saw).
 typedef int (*family_pick_fn)(tpsrhs_operator *, int, int, char *, int);
 family_pick_fn load_family(const std::string &unit) {
   static std::mutex mu;
@@ -73,6 +75,13 @@ family_pick_fn load_family(const std::string &unit) {
     const std::string path = d + "/libtpsrhs_" + unit + ".so";
     if (void *h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL)) {
       const std::string sym = "pick_" + unit;
+      // the family reads and writes the operator by its own copy of the struct: one built against another layout (a
+      // leftover of a partial build, a stray TPSRHS_FAMILY_PATH) would corrupt it silently
+      auto size = static_cast<const unsigned long *>(dlsym(h, (sym + "_operator_size").c_str()));
+      if (!size || *size != sizeof(tpsrhs_operator)) {
+        dlclose(h);
+        throw Unsupported("kernel family " + unit + " was built against another operator layout: run build() (" + path + ")");
+      }
       auto fn = reinterpret_cast<family_pick_fn>(dlsym(h, sym.c_str()));
       if (!fn) throw std::runtime_error(path + " does not export " + sym);
       loaded[unit] = fn;
@@ -88,8 +97,8 @@ family_pick_fn load_family(const std::string &unit) {
 TableDev upload_table(tpsrhs_operator *op, const tpsrhs_table &t) {
   std::vector<double> buf;
   TableDev td = table_coeffs(t, buf);
-  double *d = dev_upload(buf);
-  op->d_extra.push_back(d);
+  op->d_extra.emplace_back(DevBuf<double>(buf));
+  double *d = static_cast<double *>(op->d_extra.back().get());
   td.x = d;
   td.a = d + td.n;
   td.b = d + 2 * td.n;
@@ -105,248 +114,230 @@ void fill_plasma_params(tpsrhs_operator *op, const tpsrhs_disc *disc, const tpsr
   std::unique_ptr<ChemDev> c(new ChemDev);
   try {
     tpsrhs::fill_plasma_params<NSP>(p, *c, disc, phys, num_bcs, bcs, [op](const tpsrhs_table &t) { return upload_table(op, t); });
-  } catch (const UnsupportedConfig &e) {
+  } catch (const UnsupportedConfig &e) {  // (its header is also built alone, on the host, by tests/host_physics: it keeps its own type)
     throw Unsupported(e.what());
   }
-  ChemDev *dc = dev_alloc<ChemDev>(1);
-  HIP_CHECK(hipMemcpy(dc, c.get(), sizeof(ChemDev), hipMemcpyHostToDevice));
-  op->d_chem = dc;
-  p.chem = dc;
+  op->d_chem = DevBuf<ChemDev>(1);
+  p.chem = static_cast<ChemDev *>(op->d_chem.get());
+  HIP_CHECK(hipMemcpy(op->d_chem.get(), c.get(), sizeof(ChemDev), hipMemcpyHostToDevice));
 }
 
-// mfem::Mesh::GetElementSize(e, 1): the smallest singular value of the Jacobian at the element centre
-// (src/rhs_operator.cpp:154, src/face_integrator.cpp:253).  sqrt of the smallest eigenvalue of J^T J by cyclic
-// Jacobi rotations.  verts: [ne][2^dim][dim] lexicographic corners.
-std::vector<double> element_sizes(const std::vector<double> &verts, int dim, int ne) {
-  std::vector<double> h(ne);
-  const int nv = 1 << dim;
-  for (int e = 0; e < ne; e++) {
-    const double *V = &verts[static_cast<size_t>(e) * nv * dim];
-    double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};  // J[i][a] = d x_i / d xi_a at the centre
-    for (int v = 0; v < nv; v++)
-      for (int a = 0; a < dim; a++) {
-        const double sgn = ((v >> a) & 1) ? 1.0 : -1.0;
-        for (int i = 0; i < dim; i++) J[i][a] += sgn * V[v * dim + i] / (nv / 2);
-      }
-    double A[3][3];
-    for (int a = 0; a < dim; a++)
-      for (int b = 0; b < dim; b++) {
-        double t = 0.0;
-        for (int i = 0; i < dim; i++) t += J[i][a] * J[i][b];
-        A[a][b] = t;
-      }
-    for (int sweep = 0; sweep < 30; sweep++) {
-      double off = 0.0;
-      for (int a = 0; a < dim; a++)
-        for (int b = a + 1; b < dim; b++) off += A[a][b] * A[a][b];
-      if (off == 0.0) break;
-      for (int a = 0; a < dim; a++)
-        for (int b = a + 1; b < dim; b++) {
-          if (A[a][b] == 0.0) continue;
-          const double theta = (A[b][b] - A[a][a]) / (2.0 * A[a][b]);
-          const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-          const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
-          for (int k = 0; k < dim; k++) {  // A <- A R
-            const double aka = A[k][a], akb = A[k][b];
-            A[k][a] = c * aka - sn * akb;
-            A[k][b] = sn * aka + c * akb;
-          }
-          for (int k = 0; k < dim; k++) {  // A <- R^T A
-            const double aak = A[a][k], abk = A[b][k];
-            A[a][k] = c * aak - sn * abk;
-            A[b][k] = sn * aak + c * abk;
-          }
-        }
-    }
-    double lmin = A[0][0];
-    for (int a = 1; a < dim; a++) lmin = std::min(lmin, A[a][a]);
-    h[e] = std::sqrt(std::max(lmin, 0.0));
+// the mixture's parameter block and the kernels of its family (the plan names the shared object)
+void fill_mixture_params(tpsrhs_operator *op, const OperatorPlan &pl, const tpsrhs_disc *disc, const tpsrhs_physics *phys,
+                         int num_bcs, const tpsrhs_bc *bcs) {
+  switch (phys->mixture.num_species) {
+    case 3: fill_plasma_params<3>(op, disc, phys, num_bcs, bcs); break;
+    case 4: fill_plasma_params<4>(op, disc, phys, num_bcs, bcs); break;
+    case 5: fill_plasma_params<5>(op, disc, phys, num_bcs, bcs); break;
+    case 6: fill_plasma_params<6>(op, disc, phys, num_bcs, bcs); break;
+    case 7: fill_plasma_params<7>(op, disc, phys, num_bcs, bcs); break;
+    default: fill_plasma_params<8>(op, disc, phys, num_bcs, bcs); break;  // MAXSPECIES of the reference's device build
   }
-  return h;
+  char msg[512] = {0};
+  const int rc = load_family(pl.unit)(op, phys->mixture.two_temperature ? 1 : 0, pl.transport, msg, static_cast<int>(sizeof msg));
+  if (rc == TPSRHS_ERR_UNSUPPORTED) throw Unsupported(msg);
+  if (rc == TPSRHS_ERR_INVALID_ARGUMENT) throw std::invalid_argument(msg);
+  if (rc != TPSRHS_OK) throw DeviceError(msg);
 }
 
-// Inverse element mass matrices of the non-collocated pair: M_jk = sum_q w_q det J(q) phi_j(q) phi_k(q) with the
-// order-2p rule of the same family (MassIntegrator, src/rhs_operator.cpp:179-187), inverted per element
-// (Cholesky; the reference calls DenseMatrix::Invert, :205-212) -- the role of Me_inv, built once, on the host,
-// on all cores.  verts: [ne][2^dim][dim] lexicographic corners.
-std::vector<double> inverse_mass_matrices(const std::vector<double> &verts, int dim, int order, int ne) {
-  const Tables1D t = make_tables(order, dim, 1, 1);
-  const int n1 = order + 1, qv = rule_points(1, 2 * order);
-  const int npe = (dim == 3) ? n1 * n1 * n1 : n1 * n1, nq = (dim == 3) ? qv * qv * qv : qv * qv, nv = 1 << dim;
-  // Phi[q][j]: tensor basis at the tensor rule
-  std::vector<double> Phi(static_cast<size_t>(nq) * npe), wq(nq), xq(static_cast<size_t>(nq) * dim);
-  for (int q = 0; q < nq; q++) {
-    int qi[3] = {q % qv, (q / qv) % qv, q / (qv * qv)};
-    wq[q] = 1.0;
-    for (int d = 0; d < dim; d++) {
-      wq[q] *= t.wv[qi[d]];
-      xq[static_cast<size_t>(q) * dim + d] = t.xv[qi[d]];
+// the tables of the table gas (the plan has checked their scales and that e(T) increases)
+void upload_lte_tables(tpsrhs_operator *op, LteParams *lp, const tpsrhs_physics *phys) {
+  const tpsrhs_lte &in = phys->lte;
+  lp->tab_e = upload_table(op, in.energy_table);
+  lp->tab_R = upload_table(op, in.gas_constant_table);
+  lp->tab_c = upload_table(op, in.sound_speed_table);
+  tpsrhs_table rev = in.energy_table;  // "Construct e -> T table from T -> e", src/M2ulPhyS.cpp:193-200
+  rev.x_data = in.energy_table.f_data;
+  rev.f_data = in.energy_table.x_data;
+  lp->tab_T = upload_table(op, rev);
+  {  // search aid of the inverse table: the interval of the left edge of uniform bins over the energy axis
+    const int N = in.energy_table.n_data, nh = 4 * (N - 1);
+    const double *ex = in.energy_table.f_data;
+    const double de = (ex[N - 1] - ex[0]) / nh;
+    std::vector<int> hint(nh);
+    int idx = 0;
+    for (int j = 0; j < nh; j++) {
+      const double left = ex[0] + j * de;
+      while (idx < N - 2 && ex[idx + 1] < left) idx++;
+      hint[j] = idx;
     }
-    for (int j = 0; j < npe; j++) {
-      int ji[3] = {j % n1, (j / n1) % n1, j / (n1 * n1)};
-      double v = 1.0;
-      for (int d = 0; d < dim; d++) v *= t.Bv[qi[d] * n1 + ji[d]];
-      Phi[static_cast<size_t>(q) * npe + j] = v;
-    }
+    op->d_extra.emplace_back(DevBuf<int>(hint));
+    lp->ehint = static_cast<int *>(op->d_extra.back().get());
+    lp->nhint = nh;
+    lp->e0 = ex[0];
+    lp->inv_de = 1.0 / de;
   }
-  std::vector<double> out(static_cast<size_t>(ne) * npe * npe);
-  auto work = [&](int e_begin, int e_end) {
-    std::vector<double> M(static_cast<size_t>(npe) * npe), Wp(static_cast<size_t>(nq) * npe), L(static_cast<size_t>(npe) * npe);
-    for (int e = e_begin; e < e_end; e++) {
-      const double *V = &verts[static_cast<size_t>(e) * nv * dim];
-      for (int q = 0; q < nq; q++) {  // det J at the point (multilinear map of the 2^dim corners)
-        const double *xi = &xq[static_cast<size_t>(q) * dim];
-        double J[9] = {0};
-        for (int c = 0; c < nv; c++) {
-          for (int m2 = 0; m2 < dim; m2++) {
-            double g = 1.0;  // d/dxi_m2 of the corner's shape function
-            for (int d = 0; d < dim; d++) {
-              const int bit = (c >> d) & 1;
-              if (d == m2)
-                g *= bit ? 1.0 : -1.0;
-              else
-                g *= bit ? xi[d] : 1.0 - xi[d];
-            }
-            for (int i = 0; i < dim; i++) J[i + m2 * dim] += g * V[c * dim + i];
-          }
-        }
-        const double det = (dim == 2) ? J[0] * J[3] - J[2] * J[1]
-                                      : J[0] * (J[4] * J[8] - J[7] * J[5]) - J[3] * (J[1] * J[8] - J[7] * J[2]) +
-                                            J[6] * (J[1] * J[5] - J[4] * J[2]);
-        const double wd = wq[q] * det;
-        for (int j = 0; j < npe; j++) Wp[static_cast<size_t>(q) * npe + j] = wd * Phi[static_cast<size_t>(q) * npe + j];
-      }
-      std::fill(M.begin(), M.end(), 0.0);
-      for (int q = 0; q < nq; q++)
-        for (int j = 0; j < npe; j++) {
-          const double pj = Phi[static_cast<size_t>(q) * npe + j];
-          const double *wrow = &Wp[static_cast<size_t>(q) * npe];
-          double *mrow = &M[static_cast<size_t>(j) * npe];
-          for (int k = 0; k < npe; k++) mrow[k] += pj * wrow[k];
-        }
-      // Cholesky M = L L^T, then M^-1 = L^-T L^-1
-      std::fill(L.begin(), L.end(), 0.0);
-      for (int j = 0; j < npe; j++) {
-        double d = M[static_cast<size_t>(j) * npe + j];
-        for (int k = 0; k < j; k++) d -= L[static_cast<size_t>(j) * npe + k] * L[static_cast<size_t>(j) * npe + k];
-        if (!(d > 0.0)) throw std::runtime_error("element mass matrix is not positive definite (inverted element?)");
-        const double ljj = std::sqrt(d);
-        L[static_cast<size_t>(j) * npe + j] = ljj;
-        for (int i = j + 1; i < npe; i++) {
-          double v = M[static_cast<size_t>(i) * npe + j];
-          for (int k = 0; k < j; k++) v -= L[static_cast<size_t>(i) * npe + k] * L[static_cast<size_t>(j) * npe + k];
-          L[static_cast<size_t>(i) * npe + j] = v / ljj;
-        }
-      }
-      // Linv (lower) in M's storage
-      std::fill(M.begin(), M.end(), 0.0);
-      for (int j = 0; j < npe; j++) {
-        M[static_cast<size_t>(j) * npe + j] = 1.0 / L[static_cast<size_t>(j) * npe + j];
-        for (int i = j + 1; i < npe; i++) {
-          double v = 0.0;
-          for (int k = j; k < i; k++) v -= L[static_cast<size_t>(i) * npe + k] * M[static_cast<size_t>(k) * npe + j];
-          M[static_cast<size_t>(i) * npe + j] = v / L[static_cast<size_t>(i) * npe + i];
-        }
-      }
-      double *o = &out[static_cast<size_t>(e) * npe * npe];
-      for (int i = 0; i < npe; i++)
-        for (int j = 0; j <= i; j++) {
-          double v = 0.0;
-          for (int k = i; k < npe; k++) v += M[static_cast<size_t>(k) * npe + i] * M[static_cast<size_t>(k) * npe + j];
-          o[static_cast<size_t>(i) * npe + j] = o[static_cast<size_t>(j) * npe + i] = v;
-        }
-    }
+  auto same_grid = [](const tpsrhs_table &a, const tpsrhs_table &b) {
+    if (a.n_data != b.n_data || a.x_log_scale != b.x_log_scale) return 0;
+    for (int k = 0; k < a.n_data; k++)
+      if (a.x_data[k] != b.x_data[k]) return 0;
+    return 1;
   };
-  const int nthreads = std::max(1, std::min<int>(static_cast<int>(std::thread::hardware_concurrency()), std::min(32, ne / 64 + 1)));
-  std::vector<std::thread> pool;
-  std::vector<std::exception_ptr> errs(nthreads);
-  for (int t2 = 0; t2 < nthreads; t2++) {
-    const int b = static_cast<int>(static_cast<int64_t>(ne) * t2 / nthreads), en = static_cast<int>(static_cast<int64_t>(ne) * (t2 + 1) / nthreads);
-    pool.emplace_back([&, b, en, t2] {
-      try {
-        work(b, en);
-      } catch (...) {
-        errs[t2] = std::current_exception();
-      }
-    });
-  }
-  for (auto &th : pool) th.join();
-  for (auto &e : errs)
-    if (e) std::rethrow_exception(e);
-  return out;
+  lp->thermo_same_grid = same_grid(in.energy_table, in.gas_constant_table) && same_grid(in.energy_table, in.sound_speed_table);
+  lp->trans_same_grid = same_grid(in.viscosity_table, in.conductivity_table);
+  lp->tab_mu = upload_table(op, in.viscosity_table);
+  lp->tab_k = upload_table(op, in.conductivity_table);
+  lp->tab_sigma = upload_table(op, in.electric_conductivity_table);
+  lp->radiation = phys->radiation.model;
+  if (lp->radiation == TPSRHS_NET_EMISSION) lp->tab_nec = upload_table(op, phys->radiation.nec_table);
 }
 
+// Fluxes: sub-grid scale model and viscous sponge (src/fluxes.cpp:223-246) -> the LES flavour of the dry-air kernels
+void fill_les_params(tpsrhs_operator *op, const OperatorPlan &pl, DryAirParams &d, const tpsrhs_mesh *mesh, const tpsrhs_physics *phys) {
+  d.sgs_type = phys->sgs.model_type;
+  d.sgs_const = pl.sgs_const;
+  d.sgs_floor = phys->sgs.model_floor;
+  d.vs_enabled = pl.sponge;
+  for (int k = 0; k < 3; k++) {
+    d.vs_n[k] = pl.sponge_n[k];
+    d.vs_p[k] = pl.sponge_p[k];
+  }
+  d.vs_width = pl.sponge_width;
+  d.vs_ratio = pl.sponge_ratio;
+  const Topology &tp = op->topo;
+  std::vector<double> delta = mesh->elem_size ? std::vector<double>(mesh->elem_size, mesh->elem_size + tp.ne)
+                                              : element_sizes(tp.verts, op->dim, tp.ne);
+  for (double &v : delta) v /= op->order;  // elSize = GetElementSize(e, 1) / order, src/rhs_operator.cpp:154
+  op->d_extra.emplace_back(DevBuf<double>(delta));
+  d.elem_delta = static_cast<double *>(op->d_extra.back().get());
+}
+
+// the dry-air block, which the table gas extends (boundary conditions and switches are shared)
+void fill_single_fluid_params(tpsrhs_operator *op, const OperatorPlan &pl, const tpsrhs_mesh *mesh, const tpsrhs_disc *disc,
+                              const tpsrhs_physics *phys, int num_bcs, const tpsrhs_bc *bcs) {
+  static_assert(sizeof(LteParams) <= sizeof(op->params), "parameter block");
+  LteParams *lp = pl.lte ? new (op->params) LteParams : nullptr;
+  if (lp) std::memset(static_cast<void *>(lp), 0, sizeof(LteParams));
+  DryAirParams &d = lp ? *static_cast<DryAirParams *>(lp) : *new (op->params) DryAirParams;
+  if (!lp) std::memset(&d, 0, sizeof(d));
+  if (lp) upload_lte_tables(op, lp, phys);
+  d.gamma = phys->dry_air.specific_heat_ratio;
+  d.Rg = phys->dry_air.gas_constant;
+  d.inv_Rg = 1.0 / d.Rg;
+  d.visc_mult = phys->dry_air.visc_mult;
+  d.bulk_mult = phys->dry_air.bulk_visc_mult;
+  d.C1 = phys->dry_air.sutherland_C1;
+  d.S0 = phys->dry_air.sutherland_S0;
+  d.cp_div_pr = d.gamma * d.Rg / (phys->dry_air.sutherland_Pr * (d.gamma - 1.0));
+  d.eq_system = phys->eq_system;
+  d.use_bc_in_grad = disc->use_bc_in_grad;
+  d.use_roe = disc->use_roe ? 1 : 0;
+  d.ref_length = disc->ref_length > 0.0 ? disc->ref_length : 1.0;  // config.refLength default, run_configuration.cpp:66
+  d.num_bcs = num_bcs;
+  for (int i = 0; i < num_bcs; i++) {
+    d.bc[i].category = bcs[i].category;
+    d.bc[i].type = bcs[i].type;
+    for (int k = 0; k < 4 + TPSRHS_MAXSPECIES; k++) d.bc[i].data[k] = bcs[i].data[k];
+  }
+  if (pl.les) fill_les_params(op, pl, d, mesh, phys);
+}
+
+// vertices, face table and, for the non-collocated pair, the inverse mass matrices
+void upload_geometry(tpsrhs_operator *op) {
+  const Topology &tp = op->topo;
+  op->d_verts = DevBuf<double>(tp.verts);
+  if (op->nc) op->d_minv = DevBuf<double>(inverse_mass_matrices(tp.verts, op->dim, op->order, op->ne));
+  std::vector<int2> fi(tp.face_nbr.size());
+  for (size_t i = 0; i < fi.size(); i++) fi[i] = make_int2(tp.face_nbr[i], tp.face_orient[i]);
+  op->d_face_info = DevBuf<int2>(fi);
+}
+
+// faces of the non-reflecting patches (dry air), in slot order, and the state they carry from one Mult to the next
+void build_nr_tables(tpsrhs_operator *op, const tpsrhs_bc *bcs) {
+  const Topology &tp = op->topo;
+  std::vector<int2> nrf;
+  std::vector<int> ordinal(tp.face_nbr.size(), -1);
+  DryAirParams &d = *reinterpret_cast<DryAirParams *>(op->params);
+  for (size_t slot = 0; slot < tp.face_nbr.size(); slot++) {
+    const int nb = tp.face_nbr[slot];
+    if (nb >= 0) continue;
+    const int b = -nb - 1;
+    if (!is_non_reflecting(bcs[b].category, bcs[b].type)) continue;
+    ordinal[slot] = static_cast<int>(nrf.size());
+    nrf.push_back(make_int2(static_cast<int>(slot), b));
+    // tangent1 of the patch: the caller's (the reference takes it from its first boundary face,
+    // src/outletBC.cpp:160-172) or an edge of our first face of the patch, orthogonalised to nothing --
+    // as there, the patch is assumed planar
+    double *t1 = &d.bc[b].data[4];
+    if (t1[0] == 0.0 && t1[1] == 0.0 && t1[2] == 0.0) {
+      const int e = static_cast<int>(slot) / op->nfaces, lf = static_cast<int>(slot) % op->nfaces, D = lf >> 1, sd = lf & 1;
+      const int nv = 1 << op->dim, a = (op->dim == 2) ? 1 - D : (D == 0 ? 1 : 0);
+      const int c0 = sd << D, c1 = c0 | (1 << a);
+      double mod = 0.0, t[3] = {0, 0, 0};
+      for (int k = 0; k < op->dim; k++) {
+        t[k] = tp.verts[(static_cast<size_t>(e) * nv + c1) * op->dim + k] - tp.verts[(static_cast<size_t>(e) * nv + c0) * op->dim + k];
+        mod += t[k] * t[k];
+      }
+      for (int k = 0; k < 3; k++) t1[k] = t[k] / std::sqrt(mod);
+    }
+  }
+  if (tp.num_shared > 0 && !op->reduce)
+    throw std::runtime_error("halo: a partitioned mesh with non-reflecting patches needs runtime.reduce");
+  op->n_nr_faces = static_cast<int>(nrf.size());
+  op->d_bc_sums = DevBuf<double>(MAXBC * (TPSRHS_MAXEQUATIONS + 1));
+  HIP_CHECK(hipMemset(op->d_bc_sums.get(), 0, MAXBC * (TPSRHS_MAXEQUATIONS + 1) * sizeof(double)));
+  if (nrf.empty()) return;
+  op->d_nr_faces = DevBuf<int2>(nrf);
+  op->d_nr_ordinal = DevBuf<int>(ordinal);
+  const size_t n = nrf.size() * static_cast<size_t>(op->nq) * op->neq;
+  for (int k = 0; k < 2; k++) {
+    op->d_bstate[k] = DevBuf<double>(n);
+    HIP_CHECK(hipMemset(op->d_bstate[k].get(), 0, n * sizeof(double)));
+  }
+}
+
+// the fields every Mult works in, and the send buffer and offsets of a partitioned mesh
+void allocate_work_buffers(tpsrhs_operator *op) {
+  const Topology &tp = op->topo;
+  if (op->ndofs >= (int64_t(1) << 31)) throw Unsupported("more than 2^31 nodes per rank");
+  const int64_t nslots = static_cast<int64_t>(op->ne) * op->nfaces + tp.num_shared;
+  op->d_Up = DevBuf<double>(op->neq * op->ndofs);
+  op->d_gradUp = DevBuf<double>(op->dim * op->neq * op->ndofs);
+  op->d_TA = DevBuf<double>(nslots * 2 * op->neq * op->nf);
+  op->d_TB = DevBuf<double>(nslots * (op->neq - 1) * op->nq);
+  HIP_CHECK(hipMemset(op->d_TA.get(), 0, nslots * 2 * op->neq * op->nf * sizeof(double)));
+  HIP_CHECK(hipMemset(op->d_TB.get(), 0, nslots * (op->neq - 1) * op->nq * sizeof(double)));
+  op->d_speed = DevBuf<double>(1);
+  HIP_CHECK(hipMemset(op->d_speed.get(), 0, sizeof(double)));
+  if (tp.num_shared > 0) {
+    op->d_shared_slot = DevBuf<int32_t>(tp.shared_slot);
+    op->d_shared_orient = DevBuf<uint8_t>(tp.shared_orient);
+    const int64_t per0 = 2 * op->neq * op->nf, per1 = static_cast<int64_t>(op->neq - 1) * op->nq;
+    op->d_send = DevBuf<double>(tp.num_shared * std::max(per0, per1));
+    for (size_t i = 0; i < tp.nbr_offsets.size(); i++) {
+      op->send_off[0].push_back(tp.nbr_offsets[i] * per0);
+      op->send_off[1].push_back(tp.nbr_offsets[i] * per1);
+    }
+    op->recv_off[0] = op->send_off[0];
+    op->recv_off[1] = op->send_off[1];
+  }
+}
+
+// operator_plan.hpp keeps host copies of two predicates of the device headers: they agree on every (category, type) of
+// the public enums (checked once per process, at the first tpsrhs_create)
+static_assert(PLAN_MAXBC == MAXBC && PLAN_PLASMA_MAXBC == PLASMA_MAXBC, "operator_plan.hpp: boundary-condition limits");
+static_assert(PLAN_TRANSPORT_CONSTANT == TRANSPORT_CONSTANT && PLAN_TRANSPORT_ARGON_MINIMAL == TRANSPORT_ARGON_MINIMAL &&
+                  PLAN_TRANSPORT_ARGON_MIXTURE == TRANSPORT_ARGON_MIXTURE, "operator_plan.hpp: transport indices");
+bool plan_predicates_agree() {
+  for (int cat = TPSRHS_INLET; cat <= TPSRHS_WALL; cat++)
+    for (int type = 0; type <= TPSRHS_SUB_VEL_CONST_ENT; type++)
+      if (plan_is_non_reflecting(cat, type) != is_non_reflecting(cat, type) || plan_is_face_inlet(cat, type) != is_face_inlet(cat, type))
+        return false;
+  return true;
+}
+
+// plan (operator_plan.hpp: every refusal that needs neither a device nor the mesh) -> device -> topology -> parameter block
+// and kernels -> geometry -> non-reflecting tables -> work buffers -> timing events
 void setup(tpsrhs_operator *op, const tpsrhs_mesh *mesh, const tpsrhs_disc *disc, const tpsrhs_physics *phys,
            int num_bcs, const tpsrhs_bc *bcs, const tpsrhs_runtime *rt) {
-  // basisType / integrationRule (src/M2ulPhyS.cpp:557-572): the collocated Gauss-Legendre pair (0, 0) of the
-  // cylinder / wedge / torch inputs, or the Gauss-Lobatto pair (1, 1), the reference's defaults (:2671-2672)
-  if (disc->basis_type == TPSRHS_BASIS_GAUSS_LEGENDRE && disc->int_rule_type == 0)
-    op->nc = 0;
-  else if (disc->basis_type == TPSRHS_BASIS_GAUSS_LOBATTO && disc->int_rule_type == 1)
-    op->nc = 1;
-  else
-    throw Unsupported("basisType / integrationRule: built pairs are (0, 0) Gauss-Legendre and (1, 1) Gauss-Lobatto");
-  if (op->nc && disc->axisymmetric) throw Unsupported("the Gauss-Lobatto pair is built for the planar 2-D and the 3-D formulation");
-  const bool plasma = phys->working_fluid == TPSRHS_USER_DEFINED;
-  if (disc->axisymmetric && mesh->dim != 2) throw std::invalid_argument("the axisymmetric formulation needs a 2-D mesh");
-  const bool lte = phys->working_fluid == TPSRHS_LTE_FLUID;
-  if (phys->working_fluid != TPSRHS_DRY_AIR && !plasma && !lte) throw std::invalid_argument("unknown working_fluid");
-  if (lte && (!disc->axisymmetric || op->nc))
-    throw Unsupported("WorkingFluid::LTE_FLUID (one-dimensional tables): built for the axisymmetric formulation, Gauss-Legendre pair");
-  if (disc->use_roe && (mesh->dim != 2 || disc->axisymmetric || plasma || lte))
-    throw Unsupported("flow/useRoe: Eval_Roe of the reference is 2-D, single-species, not axisymmetric "
-                      "(src/riemann_solver.cpp:117-206)");
-  if (phys->eq_system != TPSRHS_EULER && phys->eq_system != TPSRHS_NS) throw Unsupported("NS_PASSIVE is out of scope");
-  if (num_bcs > (plasma ? PLASMA_MAXBC : MAXBC)) throw Unsupported("too many boundary conditions");
-  for (int i = 0; i < num_bcs; i++) {
-    const tpsrhs_bc &b = bcs[i];
-    const bool nr = is_non_reflecting(b.category, b.type);
-    if (nr && (plasma || lte || disc->axisymmetric))
-      throw Unsupported("non-reflecting inlet/outlet types: perfect gas (dry air), not axisymmetric -- the reference's "
-                        "characteristic algebra (src/outletBC.cpp:573-1027)");
-    if (nr && (b.type == TPSRHS_SUB_MF_NR || b.type == TPSRHS_SUB_MF_NR_PW) && !(b.data[7] > 0.0))
-      throw std::invalid_argument("mass-flow outlet: data[7] must hold the total patch area");
-    const bool face_inlet = is_face_inlet(b.category, b.type);
-    if (face_inlet && (mesh->dim != 3 || disc->axisymmetric))
-      throw Unsupported("face-relative inlets (subsonicFaceBasedX/Y/Z): 3-D (the reference's face frame has three components)");
-    const bool ok = nr || face_inlet || (b.category == TPSRHS_INLET && b.type == TPSRHS_SUB_DENS_VEL) ||
-                    (b.category == TPSRHS_OUTLET && b.type == TPSRHS_SUB_P) ||
-                    (b.category == TPSRHS_WALL &&
-                     (b.type == TPSRHS_INV || b.type == TPSRHS_SLIP || b.type == TPSRHS_VISC_ADIAB || b.type == TPSRHS_VISC_ISOTH ||
-                      (b.type == TPSRHS_VISC_GNRL && plasma)));
-    if (!ok) throw Unsupported("boundary condition type outside the hot-path scope (attribute " + std::to_string(b.attribute) + ")");
-    if (b.category == TPSRHS_WALL && b.type == TPSRHS_VISC_GNRL) {
-      // the combinations the reference's input parser lets through (src/M2ulPhyS.cpp:3515-3582)
-      const int hc = static_cast<int>(b.data[2]), ec = static_cast<int>(b.data[3]);
-      const bool two_t = phys->mixture.two_temperature != 0;
-      const bool hvy_ok = (hc == TPSRHS_ISOTH || hc == TPSRHS_ADIAB);
-      const bool elec_ok = two_t ? (ec == TPSRHS_ISOTH || ec == TPSRHS_ADIAB || ec == TPSRHS_SHTH) : (ec == TPSRHS_SHTH);
-      if (!hvy_ok) throw std::invalid_argument("viscous_general wall: heavy thermal condition must be isothermal or adiabatic");
-      if (!elec_ok)
-        throw std::invalid_argument("viscous_general wall: electron thermal condition not understood "
-                                    "(single-temperature plasmas accept the sheath condition only)");
-      if (ec == TPSRHS_SHTH && !phys->mixture.ambipolar)
-        throw std::invalid_argument("viscous_general wall: plasma must be ambipolar for the sheath condition");
-    }
-  }
-  op->dim = mesh->dim;
-  op->order = disc->order;
-  op->nvel = disc->axisymmetric ? 3 : op->dim;
-  op->neq = op->nvel + 2;
-  if (plasma) {
-    const tpsrhs_perfect_mixture &mx = phys->mixture;
-    if (!mx.is_electron_included) throw Unsupported("USER_DEFINED fluids without electrons are not built");
-    if (mx.num_species < 3 || mx.num_species > TPSRHS_MAXSPECIES)
-      throw Unsupported("USER_DEFINED fluids: 3 to 8 species (electron, background and 1 to 6 others)");
-    if (mx.num_species > 7 && phys->transport_model == TPSRHS_ARGON_MIXTURE)  // the reference asserts, src/gas_transport.cpp:905-911
-      throw Unsupported("argon_mixture transport supports at most 7 species (Ar, Ar.+1, Ar_m, Ar_r, Ar_p, Ar_h, E)");
-    if (mx.num_species != 3 && phys->transport_model == TPSRHS_ARGON_MINIMAL)
-      throw Unsupported("argon_minimal transport is the ternary (Ar, Ar.+1, E) model");
-    if (phys->transport_model != TPSRHS_CONSTANT && phys->transport_model != TPSRHS_ARGON_MINIMAL &&
-        phys->transport_model != TPSRHS_ARGON_MIXTURE)
-      throw Unsupported("transport model outside the built scope (constant, argon_minimal, argon_mixture)");
-    op->neq = op->nvel + 2 + (mx.ambipolar ? mx.num_species - 2 : mx.num_species - 1) + (mx.two_temperature ? 1 : 0);
-  }
+  static const bool agree = plan_predicates_agree();
+  if (!agree) throw std::logic_error("operator_plan.hpp and the device headers disagree about a boundary-condition predicate");
+  const OperatorPlan pl = plan_operator(mesh->dim, *disc, *phys, num_bcs, bcs);
+  op->nc = pl.nc;
+  op->dim = pl.dim;
+  op->order = pl.order;
+  op->nvel = pl.nvel;
+  op->neq = pl.neq;
   op->phys = *phys;
 
   int ndev = 0;
@@ -377,249 +368,34 @@ void setup(tpsrhs_operator *op, const tpsrhs_mesh *mesh, const tpsrhs_disc *disc
   const int npe = (op->dim == 3) ? n1 * n1 * n1 : n1 * n1;
   op->ndofs = static_cast<int64_t>(op->ne) * npe;
 
-  // Viscous sponge of the 2-D kernels with the heavy interface (the mixtures planar and axisymmetric, axisymmetric dry air
-  // and table gas): the plane travels in MeshDev, the closures scale their coefficients (src/fluxes.cpp:232-246)
-  const bool heavy2d = op->dim == 2 && (plasma || disc->axisymmetric);
-  if ((plasma || lte || disc->axisymmetric) && phys->sgs.model_type != TPSRHS_SGS_NONE)
-    throw Unsupported("sub-grid scale models: built for dry air in 3-D");
-  if (phys->visc_sponge.enabled && (plasma || lte || disc->axisymmetric)) {
-    if (!heavy2d || op->nc)
-      throw Unsupported("viscous sponge for mixtures: built for the planar 2-D and the axisymmetric formulation, Gauss-Legendre pair");
-    const tpsrhs_visc_sponge &v = phys->visc_sponge;
-    if (!(v.width > 0.0)) throw std::invalid_argument("visc_sponge.width must be positive");
-    const double nmag = std::sqrt(v.normal[0] * v.normal[0] + v.normal[1] * v.normal[1]);  // normalised: src/fluxes.cpp:77-90
-    if (!(nmag > 0.0)) throw std::invalid_argument("visc_sponge.normal is zero");
+  if (pl.heavy2d && pl.sponge) {  // the plane travels in MeshDev, the closures scale their coefficients (src/fluxes.cpp:232-246)
     op->vs2d.enabled = 1;
     for (int k = 0; k < 2; k++) {
-      op->vs2d.n[k] = v.normal[k] / nmag;
-      op->vs2d.p[k] = v.point[k];
+      op->vs2d.n[k] = pl.sponge_n[k];
+      op->vs2d.p[k] = pl.sponge_p[k];
     }
-    op->vs2d.width = v.width;
-    op->vs2d.ratio = v.ratio;
+    op->vs2d.width = pl.sponge_width;
+    op->vs2d.ratio = pl.sponge_ratio;
   }
-  if (plasma) {
-    const int nsp = phys->mixture.num_species;
-    const bool ambi = phys->mixture.ambipolar != 0, two_t = phys->mixture.two_temperature != 0;
-    switch (nsp) {
-      case 3: fill_plasma_params<3>(op, disc, phys, num_bcs, bcs); break;
-      case 4: fill_plasma_params<4>(op, disc, phys, num_bcs, bcs); break;
-      case 5: fill_plasma_params<5>(op, disc, phys, num_bcs, bcs); break;
-      case 6: fill_plasma_params<6>(op, disc, phys, num_bcs, bcs); break;
-      case 7: fill_plasma_params<7>(op, disc, phys, num_bcs, bcs); break;
-      default: fill_plasma_params<8>(op, disc, phys, num_bcs, bcs); break;  // MAXSPECIES of the reference's device build
-    }
-    const int tr = (phys->transport_model == TPSRHS_CONSTANT)
-                       ? TRANSPORT_CONSTANT
-                       : (phys->transport_model == TPSRHS_ARGON_MINIMAL ? TRANSPORT_ARGON_MINIMAL : TRANSPORT_ARGON_MIXTURE);
-    // one shared object per (geometry, species count, ambipolar) family, and a second one for the polynomial orders
-    // 4 and 5: every species count up to MAXSPECIES = 8 (MAXEQUATIONS = 13) of the reference's device build
-    // (src/dataStructures.hpp:41-65), ambipolar or not
-    const char *geo = (op->dim == 3) ? "3d" : (disc->axisymmetric ? "axi" : "2d");
-    const std::string unit = std::string("plasma_") + geo + "_n" + std::to_string(nsp) + (ambi ? "a" : "") + ((op->order >= 4 && !op->nc) ? "_hi" : "");
-    char msg[512] = {0};
-    const int rc = load_family(unit)(op, two_t ? 1 : 0, tr, msg, static_cast<int>(sizeof msg));
-    if (rc == TPSRHS_ERR_UNSUPPORTED) throw Unsupported(msg);
-    if (rc == TPSRHS_ERR_INVALID_ARGUMENT) throw std::invalid_argument(msg);
-    if (rc != TPSRHS_OK) throw DeviceError(msg);
+  if (pl.plasma) {
+    fill_mixture_params(op, pl, disc, phys, num_bcs, bcs);
   } else {
-    // (the table gas extends the dry-air block: boundary conditions and switches are shared)
-    static_assert(sizeof(LteParams) <= sizeof(op->params), "parameter block");
-    LteParams *lp = lte ? new (op->params) LteParams : nullptr;
-    if (lp) std::memset(static_cast<void *>(lp), 0, sizeof(LteParams));
-    DryAirParams &d = lp ? *static_cast<DryAirParams *>(lp) : *new (op->params) DryAirParams;
-    if (!lp) std::memset(&d, 0, sizeof(d));
-    if (lp) {
-      const tpsrhs_lte &in = phys->lte;
-      // LinearTable with xLogScale = fLogScale = false, as the reference hard-codes for these tables (src/M2ulPhyS.cpp:176-255);
-      // the inverse table T(e) below and its search aid assume linear axes
-      for (const tpsrhs_table *t : {&in.energy_table, &in.gas_constant_table, &in.sound_speed_table, &in.viscosity_table,
-                                    &in.conductivity_table, &in.electric_conductivity_table})
-        if (t->x_log_scale || t->f_log_scale) throw std::invalid_argument("lte tables: linear scales only (x_log_scale = f_log_scale = 0)");
-      lp->tab_e = upload_table(op, in.energy_table);
-      lp->tab_R = upload_table(op, in.gas_constant_table);
-      lp->tab_c = upload_table(op, in.sound_speed_table);
-      for (int k = 1; k < in.energy_table.n_data; k++)
-        if (!(in.energy_table.f_data[k] > in.energy_table.f_data[k - 1]))
-          throw std::invalid_argument("lte.energy_table: e(T) must increase (the inverse table T(e) is its transpose)");
-      tpsrhs_table rev = in.energy_table;  // "Construct e -> T table from T -> e", src/M2ulPhyS.cpp:193-200
-      rev.x_data = in.energy_table.f_data;
-      rev.f_data = in.energy_table.x_data;
-      lp->tab_T = upload_table(op, rev);
-      {  // search aid of the inverse table: the interval of the left edge of uniform bins over the energy axis
-        const int N = in.energy_table.n_data, nh = 4 * (N - 1);
-        const double *ex = in.energy_table.f_data;
-        const double de = (ex[N - 1] - ex[0]) / nh;
-        std::vector<int> hint(nh);
-        int idx = 0;
-        for (int j = 0; j < nh; j++) {
-          const double left = ex[0] + j * de;
-          while (idx < N - 2 && ex[idx + 1] < left) idx++;
-          hint[j] = idx;
-        }
-        int *dh = dev_upload(hint);
-        op->d_extra.push_back(dh);
-        lp->ehint = dh;
-        lp->nhint = nh;
-        lp->e0 = ex[0];
-        lp->inv_de = 1.0 / de;
-      }
-      auto same_grid = [](const tpsrhs_table &a, const tpsrhs_table &b) {
-        if (a.n_data != b.n_data || a.x_log_scale != b.x_log_scale) return 0;
-        for (int k = 0; k < a.n_data; k++)
-          if (a.x_data[k] != b.x_data[k]) return 0;
-        return 1;
-      };
-      lp->thermo_same_grid = same_grid(in.energy_table, in.gas_constant_table) && same_grid(in.energy_table, in.sound_speed_table);
-      lp->trans_same_grid = same_grid(in.viscosity_table, in.conductivity_table);
-      lp->tab_mu = upload_table(op, in.viscosity_table);
-      lp->tab_k = upload_table(op, in.conductivity_table);
-      lp->tab_sigma = upload_table(op, in.electric_conductivity_table);
-      lp->radiation = phys->radiation.model;
-      if (lp->radiation == TPSRHS_NET_EMISSION) lp->tab_nec = upload_table(op, phys->radiation.nec_table);
-    }
-    d.gamma = phys->dry_air.specific_heat_ratio;
-    d.Rg = phys->dry_air.gas_constant;
-    d.inv_Rg = 1.0 / d.Rg;
-    d.visc_mult = phys->dry_air.visc_mult;
-    d.bulk_mult = phys->dry_air.bulk_visc_mult;
-    d.C1 = phys->dry_air.sutherland_C1;
-    d.S0 = phys->dry_air.sutherland_S0;
-    d.cp_div_pr = d.gamma * d.Rg / (phys->dry_air.sutherland_Pr * (d.gamma - 1.0));
-    d.eq_system = phys->eq_system;
-    d.use_bc_in_grad = disc->use_bc_in_grad;
-    d.use_roe = disc->use_roe ? 1 : 0;
-    d.ref_length = disc->ref_length > 0.0 ? disc->ref_length : 1.0;  // config.refLength default, run_configuration.cpp:66
-    d.num_bcs = num_bcs;
-    for (int i = 0; i < num_bcs; i++) {
-      d.bc[i].category = bcs[i].category;
-      d.bc[i].type = bcs[i].type;
-      for (int k = 0; k < 4 + TPSRHS_MAXSPECIES; k++) d.bc[i].data[k] = bcs[i].data[k];
-    }
-    bool any_nr = false;
-    for (int i = 0; i < num_bcs; i++) any_nr = any_nr || is_non_reflecting(bcs[i].category, bcs[i].type);
-    // Fluxes: sub-grid scale model and viscous sponge (src/fluxes.cpp:223-246) -> the LES flavour of the kernels
-    const bool les = !heavy2d && (phys->sgs.model_type != TPSRHS_SGS_NONE || phys->visc_sponge.enabled);
-    if (les) {
-      if (phys->sgs.model_type < 0 || phys->sgs.model_type > TPSRHS_SGS_SIGMA)
-        throw std::invalid_argument("unknown sgs.model_type");
-      if (disc->axisymmetric || op->nc || any_nr)
-        throw Unsupported("sub-grid scale model / viscous sponge: built for dry air, planar 2-D and 3-D, Gauss-Legendre pair, "
-                          "reflecting boundary types");
-      if (phys->sgs.model_type != TPSRHS_SGS_NONE && op->dim != 3)
-        throw Unsupported("sub-grid scale models need dim == 3 (the reference's strain tensor indexes three directions)");
-      if (phys->visc_sponge.enabled && !(phys->visc_sponge.width > 0.0))
-        throw std::invalid_argument("visc_sponge.width must be positive");
-      d.sgs_type = phys->sgs.model_type;
-      d.sgs_const = phys->sgs.model_const > 0.0 ? phys->sgs.model_const  // defaults of src/M2ulPhyS.cpp:2693-2698
-                                                : (d.sgs_type == TPSRHS_SGS_SMAGORINSKY ? 0.12 : (d.sgs_type == TPSRHS_SGS_SIGMA ? 0.135 : 0.0));
-      d.sgs_floor = phys->sgs.model_floor;
-      d.vs_enabled = phys->visc_sponge.enabled ? 1 : 0;
-      // "ensure normal is actually a unit normal": the constructor every CPU build of the reference uses, and its host
-      // fluxClass, normalise vsd_.n (src/fluxes.cpp:77-90, src/M2ulPhyS.cpp:612-616); the device constructor
-      // (:98-125) copies it as given.  The CPU path is this library's referent.
-      double nmag = 0.0;
-      for (int k = 0; k < op->dim; k++) nmag += phys->visc_sponge.normal[k] * phys->visc_sponge.normal[k];
-      nmag = std::sqrt(nmag);
-      if (phys->visc_sponge.enabled && !(nmag > 0.0)) throw std::invalid_argument("visc_sponge.normal is zero");
-      for (int k = 0; k < 3; k++) {
-        d.vs_n[k] = (k < op->dim && nmag > 0.0) ? phys->visc_sponge.normal[k] / nmag : 0.0;  // vsd.n / vsd.p: dim entries, the rest 0
-        d.vs_p[k] = (k < op->dim) ? phys->visc_sponge.point[k] : 0.0;
-      }
-      d.vs_width = phys->visc_sponge.enabled ? phys->visc_sponge.width : 1.0;
-      d.vs_ratio = phys->visc_sponge.enabled ? phys->visc_sponge.ratio : 1.0;
-      std::vector<double> delta = mesh->elem_size ? std::vector<double>(mesh->elem_size, mesh->elem_size + tp.ne)
-                                                  : element_sizes(tp.verts, op->dim, tp.ne);
-      for (double &v : delta) v /= op->order;  // elSize = GetElementSize(e, 1) / order, src/rhs_operator.cpp:154
-      double *dd = dev_upload(delta);
-      op->d_extra.push_back(dd);
-      d.elem_delta = dd;
+    fill_single_fluid_params(op, pl, mesh, disc, phys, num_bcs, bcs);
+    if (pl.les)
       pick_dryair_les(op);
-    } else if (lte)
+    else if (pl.lte)
       pick_lte_axisym(op);
     else if (disc->axisymmetric)
       pick_dryair_axisym(op);
     else if (op->dim == 3)
-      any_nr ? pick_order<3, DryAirPhys<3, true>>(op) : pick_order<3, DryAirPhys<3>>(op);
+      pl.any_nr ? pick_order<3, DryAirPhys<3, true>>(op) : pick_order<3, DryAirPhys<3>>(op);
     else
-      any_nr ? pick_order<2, DryAirPhys<2, true>>(op) : pick_order<2, DryAirPhys<2>>(op);
+      pl.any_nr ? pick_order<2, DryAirPhys<2, true>>(op) : pick_order<2, DryAirPhys<2>>(op);
   }
-
-  op->d_verts = dev_upload(tp.verts);
-  if (op->nc) op->d_minv = dev_upload(inverse_mass_matrices(tp.verts, op->dim, op->order, op->ne));
-  {
-    std::vector<int2> fi(tp.face_nbr.size());
-    for (size_t i = 0; i < fi.size(); i++) fi[i] = make_int2(tp.face_nbr[i], tp.face_orient[i]);
-    op->d_face_info = dev_upload(fi);
-  }
-  if (!plasma && !disc->axisymmetric) {  // faces of the non-reflecting patches, in slot order
-    std::vector<int2> nrf;
-    std::vector<int> ordinal(tp.face_nbr.size(), -1);
-    bool any_nr = false;
-    for (int i = 0; i < num_bcs; i++) any_nr = any_nr || is_non_reflecting(bcs[i].category, bcs[i].type);
-    if (any_nr) {
-      DryAirParams &d = *reinterpret_cast<DryAirParams *>(op->params);
-      for (size_t slot = 0; slot < tp.face_nbr.size(); slot++) {
-        const int nb = tp.face_nbr[slot];
-        if (nb >= 0) continue;
-        const int b = -nb - 1;
-        if (!is_non_reflecting(bcs[b].category, bcs[b].type)) continue;
-        ordinal[slot] = static_cast<int>(nrf.size());
-        nrf.push_back(make_int2(static_cast<int>(slot), b));
-        // tangent1 of the patch: the caller's (the reference takes it from its first boundary face,
-        // src/outletBC.cpp:160-172) or an edge of our first face of the patch, orthogonalised to nothing --
-        // as there, the patch is assumed planar
-        double *t1 = &d.bc[b].data[4];
-        if (t1[0] == 0.0 && t1[1] == 0.0 && t1[2] == 0.0) {
-          const int e = static_cast<int>(slot) / op->nfaces, lf = static_cast<int>(slot) % op->nfaces, D = lf >> 1, sd = lf & 1;
-          const int nv = 1 << op->dim, a = (op->dim == 2) ? 1 - D : (D == 0 ? 1 : 0);
-          const int c0 = sd << D, c1 = c0 | (1 << a);
-          double mod = 0.0, t[3] = {0, 0, 0};
-          for (int k = 0; k < op->dim; k++) {
-            t[k] = tp.verts[(static_cast<size_t>(e) * nv + c1) * op->dim + k] - tp.verts[(static_cast<size_t>(e) * nv + c0) * op->dim + k];
-            mod += t[k] * t[k];
-          }
-          for (int k = 0; k < 3; k++) t1[k] = t[k] / std::sqrt(mod);
-        }
-      }
-      if (tp.num_shared > 0 && !op->reduce)
-        throw std::runtime_error("halo: a partitioned mesh with non-reflecting patches needs runtime.reduce");
-      op->n_nr_faces = static_cast<int>(nrf.size());
-      op->d_bc_sums = dev_alloc<double>(MAXBC * (TPSRHS_MAXEQUATIONS + 1));
-      HIP_CHECK(hipMemset(op->d_bc_sums, 0, MAXBC * (TPSRHS_MAXEQUATIONS + 1) * sizeof(double)));
-      if (!nrf.empty()) {
-        op->d_nr_faces = dev_upload(nrf);
-        op->d_nr_ordinal = dev_upload(ordinal);
-        const size_t n = nrf.size() * static_cast<size_t>(op->nq) * op->neq;
-        for (int k = 0; k < 2; k++) {
-          op->d_bstate[k] = dev_alloc<double>(n);
-          HIP_CHECK(hipMemset(op->d_bstate[k], 0, n * sizeof(double)));
-        }
-      }
-    }
-    op->has_nr = any_nr;
-  }
-  if (op->ndofs >= (int64_t(1) << 31)) throw Unsupported("more than 2^31 nodes per rank");
-  const int64_t nslots = static_cast<int64_t>(op->ne) * op->nfaces + tp.num_shared;
-  op->d_Up = dev_alloc<double>(op->neq * op->ndofs);
-  op->d_gradUp = dev_alloc<double>(op->dim * op->neq * op->ndofs);
-  op->d_TA = dev_alloc<double>(nslots * 2 * op->neq * op->nf);
-  op->d_TB = dev_alloc<double>(nslots * (op->neq - 1) * op->nq);
-  HIP_CHECK(hipMemset(op->d_TA, 0, nslots * 2 * op->neq * op->nf * sizeof(double)));
-  HIP_CHECK(hipMemset(op->d_TB, 0, nslots * (op->neq - 1) * op->nq * sizeof(double)));
-  op->d_speed = dev_alloc<double>(1);
-  HIP_CHECK(hipMemset(op->d_speed, 0, sizeof(double)));
-  if (tp.num_shared > 0) {
-    op->d_shared_slot = dev_upload(tp.shared_slot);
-    op->d_shared_orient = dev_upload(tp.shared_orient);
-    const int64_t per0 = 2 * op->neq * op->nf, per1 = static_cast<int64_t>(op->neq - 1) * op->nq;
-    op->d_send = dev_alloc<double>(tp.num_shared * std::max(per0, per1));
-    for (size_t i = 0; i < tp.nbr_offsets.size(); i++) {
-      op->send_off[0].push_back(tp.nbr_offsets[i] * per0);
-      op->send_off[1].push_back(tp.nbr_offsets[i] * per1);
-    }
-    op->recv_off[0] = op->send_off[0];
-    op->recv_off[1] = op->send_off[1];
-  }
+  upload_geometry(op);
+  if (pl.any_nr) build_nr_tables(op, bcs);
+  op->has_nr = pl.any_nr;
+  allocate_work_buffers(op);
   for (auto &set : op->evs)
     for (auto &e : set) HIP_CHECK(hipEventCreate(&e));
 }
@@ -733,9 +509,9 @@ int tpsrhs_mult(tpsrhs_handle h, const double *x, double *y, double /*time*/, do
     HIP_CHECK(hipSetDevice(h->device));
     h->launch(h, x, y, false);
     if (max_char_speed) {
-      hipLaunchKernelGGL(k_reduce_max<1024>, dim3(1), dim3(1024), 0, h->stream, h->flux_grid, h->d_block_speed, h->d_speed);
+      hipLaunchKernelGGL(k_reduce_max<1024>, dim3(1), dim3(1024), 0, h->stream, h->flux_grid, h->d_block_speed.get(), h->d_speed.get());
       HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipMemcpyAsync(max_char_speed, h->d_speed, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIP_CHECK(hipMemcpyAsync(max_char_speed, h->d_speed.get(), sizeof(double), hipMemcpyDeviceToHost, h->stream));
       HIP_CHECK(hipStreamSynchronize(h->stream));
     }
   });
@@ -747,16 +523,16 @@ int tpsrhs_mult_host(tpsrhs_handle h, const double *x, double *y, double time, d
   int st = guarded([&] {
     HIP_CHECK(hipSetDevice(h->device));
     if (!h->d_xh) {
-      h->d_xh = dev_alloc<double>(h->neq * h->ndofs);
-      h->d_yh = dev_alloc<double>(h->neq * h->ndofs);
+      h->d_xh = DevBuf<double>(h->neq * h->ndofs);
+      h->d_yh = DevBuf<double>(h->neq * h->ndofs);
     }
-    HIP_CHECK(hipMemcpyAsync(h->d_xh, x, bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipMemcpyAsync(h->d_xh.get(), x, bytes, hipMemcpyHostToDevice, h->stream));
   });
   if (st != TPSRHS_OK) return st;
-  st = tpsrhs_mult(h, h->d_xh, h->d_yh, time, max_char_speed);
+  st = tpsrhs_mult(h, h->d_xh.get(), h->d_yh.get(), time, max_char_speed);
   if (st != TPSRHS_OK) return st;
   return guarded([&] {
-    HIP_CHECK(hipMemcpyAsync(y, h->d_yh, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipMemcpyAsync(y, h->d_yh.get(), bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(hipStreamSynchronize(h->stream));
   });
 }
@@ -766,11 +542,11 @@ namespace {
 void rk4_stages(tpsrhs_operator *h, double *x, double dt, const double *dt_dev) {
   const int64_t n = static_cast<int64_t>(h->neq) * h->ndofs;
   if (!h->d_rk) {
-    h->d_rk = dev_alloc<double>(3 * n);
-    h->d_nan = dev_alloc<unsigned long long>(1);
-    HIP_CHECK(hipMemsetAsync(h->d_nan, 0, sizeof(unsigned long long), h->stream));
+    h->d_rk = DevBuf<double>(3 * n);
+    h->d_nan = DevBuf<unsigned long long>(1);
+    HIP_CHECK(hipMemsetAsync(h->d_nan.get(), 0, sizeof(unsigned long long), h->stream));
   }
-  double *k = h->d_rk, *y = k + n, *z = y + n;
+  double *k = h->d_rk.get(), *y = k + n, *z = y + n;
   if (!h->ta_chain) h->ta_valid = false;  // a step starts with its own k_traces sweep: x may have been touched since the
                                           // last call (tpsrhs_advance chains its steps: nothing touches x between them)
   const bool mixture = h->phys.working_fluid == TPSRHS_USER_DEFINED;
@@ -798,7 +574,7 @@ void rk4_stages(tpsrhs_operator *h, double *x, double dt, const double *dt_dev) 
       r.y3 = y3;
       r.y4 = y4;
       r.out = outs[stage - 1];
-      r.nan_count = h->d_nan;
+      r.nan_count = h->d_nan.get();
       h->rk = r;
       try {
         h->launch(h, ins[stage - 1], outs[stage - 1], false);
@@ -816,7 +592,7 @@ void rk4_stages(tpsrhs_operator *h, double *x, double dt, const double *dt_dev) 
   for (int stage = 1; stage <= 4; stage++) {
     h->launch(h, in, k, false);  // k_s = f(stage input); SetTime is a no-op for this operator
     hipLaunchKernelGGL(k_rk4_stage<256>, dim3(grid), dim3(256), 0, h->stream, stage, n, h->ndofs, sp_first, sp_last, dt,
-                       dt_dev, x, k, y, z, h->d_nan);
+                       dt_dev, x, k, y, z, h->d_nan.get());
     HIP_CHECK(hipGetLastError());
     in = y;
   }
@@ -883,16 +659,16 @@ int step_with(tpsrhs_handle h, int integrator, const char *who, double *x, doubl
   return guarded([&] {
     HIP_CHECK(hipSetDevice(h->device));
     h->nr_dt = dt;  // the boundary conditions see M2ulPhyS::dt (src/BoundaryCondition.hpp:54)
-    if (h->d_nan) HIP_CHECK(hipMemsetAsync(h->d_nan, 0, sizeof(unsigned long long), h->stream));
+    if (h->d_nan.get()) HIP_CHECK(hipMemsetAsync(h->d_nan.get(), 0, sizeof(unsigned long long), h->stream));
     step_stages(h, integrator, x, dt, nullptr);
     *time += dt;
     if (max_char_speed || nan_count) {
-      hipLaunchKernelGGL(k_reduce_max<1024>, dim3(1), dim3(1024), 0, h->stream, h->flux_grid, h->d_block_speed, h->d_speed);
+      hipLaunchKernelGGL(k_reduce_max<1024>, dim3(1), dim3(1024), 0, h->stream, h->flux_grid, h->d_block_speed.get(), h->d_speed.get());
       HIP_CHECK(hipGetLastError());
       double speed = 0.0;
       unsigned long long bad = 0;
-      HIP_CHECK(hipMemcpyAsync(&speed, h->d_speed, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      HIP_CHECK(hipMemcpyAsync(&bad, h->d_nan, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+      HIP_CHECK(hipMemcpyAsync(&speed, h->d_speed.get(), sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIP_CHECK(hipMemcpyAsync(&bad, h->d_nan.get(), sizeof(bad), hipMemcpyDeviceToHost, h->stream));
       HIP_CHECK(hipStreamSynchronize(h->stream));
       if (max_char_speed) *max_char_speed = speed;
       if (nan_count) *nan_count = static_cast<int64_t>(bad);
@@ -912,19 +688,19 @@ int advance_with(tpsrhs_handle h, int integrator, const char *who, double *x, do
     HIP_CHECK(hipSetDevice(h->device));
     if (!constant_dt && h->topo.num_shared > 0 && !h->reduce)
       throw std::runtime_error("halo: a variable time step on a partitioned mesh needs runtime.reduce");
-    if (!h->d_ctl) h->d_ctl = dev_alloc<double>(3);
+    if (!h->d_ctl) h->d_ctl = DevBuf<double>(3);
     const double ctl0[3] = {*dt, *time, 0.0};
-    HIP_CHECK(hipMemcpyAsync(h->d_ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipMemcpyAsync(h->d_ctl.get(), ctl0, sizeof(ctl0), hipMemcpyHostToDevice, h->stream));
     HIP_CHECK(hipStreamSynchronize(h->stream));  // ctl0 lives on this stack frame
-    if (h->d_nan) HIP_CHECK(hipMemsetAsync(h->d_nan, 0, sizeof(unsigned long long), h->stream));
-    h->nr_dt_dev = h->d_ctl;
+    if (h->d_nan.get()) HIP_CHECK(hipMemsetAsync(h->d_nan.get(), 0, sizeof(unsigned long long), h->stream));
+    h->nr_dt_dev = h->d_ctl.get();
     auto one_step = [&] {
-      step_stages(h, integrator, x, 0.0, h->d_ctl);
-      hipLaunchKernelGGL(k_step_end<1024>, dim3(1), dim3(1024), 0, h->stream, h->flux_grid, h->d_block_speed, h->d_ctl,
+      step_stages(h, integrator, x, 0.0, h->d_ctl.get());
+      hipLaunchKernelGGL(k_step_end<1024>, dim3(1), dim3(1024), 0, h->stream, h->flux_grid, h->d_block_speed.get(), h->d_ctl.get(),
                          constant_dt ? 1 : 0, cfl * hmin / static_cast<double>(h->dim));
       HIP_CHECK(hipGetLastError());
       if (!constant_dt && h->reduce && h->topo.num_shared > 0) {  // MPI_Allreduce(MIN) of src/M2ulPhyS.cpp:2015
-        if (h->reduce(h->reduce_ctx, h->d_ctl, 1, TPSRHS_REDUCE_MIN, h->stream) != 0)
+        if (h->reduce(h->reduce_ctx, h->d_ctl.get(), 1, TPSRHS_REDUCE_MIN, h->stream) != 0)
           throw std::runtime_error("halo: reduce callback failed");
       }
     };
@@ -1003,8 +779,8 @@ int advance_with(tpsrhs_handle h, int integrator, const char *who, double *x, do
     h->ta_chain = h->ta_valid = false;  // the caller owns x again
     double ctl[3] = {0, 0, 0};
     unsigned long long bad = 0;
-    HIP_CHECK(hipMemcpyAsync(ctl, h->d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, h->stream));
-    if (h->d_nan) HIP_CHECK(hipMemcpyAsync(&bad, h->d_nan, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipMemcpyAsync(ctl, h->d_ctl.get(), sizeof(ctl), hipMemcpyDeviceToHost, h->stream));
+    if (h->d_nan.get()) HIP_CHECK(hipMemcpyAsync(&bad, h->d_nan.get(), sizeof(bad), hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(hipStreamSynchronize(h->stream));
     *dt = ctl[0];
     *time = ctl[1];
@@ -1028,14 +804,9 @@ void upload_forcing(tpsrhs_operator *h) {
   h->forcing_active = f.has_pg || f.nheat > 0 || f.nsponge > 0 || f.nps > 0 || f.joule != nullptr;
   if (!h->forcing_active) return;
   HIP_CHECK(hipSetDevice(h->device));
-  if (!h->d_forcing) h->d_forcing = dev_alloc<ForcingDev>(1);
+  if (!h->d_forcing) h->d_forcing = DevBuf<ForcingDev>(1);
   HIP_CHECK(hipStreamSynchronize(h->stream));  // an earlier Mult may still read the block
-  HIP_CHECK(hipMemcpy(h->d_forcing, &h->forcing, sizeof(ForcingDev), hipMemcpyHostToDevice));
-}
-
-// the buffers of one forcing's mixed-out zones, in the form tpsrhs_operator::d_mixed_out keeps them
-void free_mixed_out(const std::vector<void *> &v) {
-  for (void *q : v) (void)hipFree(q);
+  HIP_CHECK(hipMemcpy(h->d_forcing.get(), &h->forcing, sizeof(ForcingDev), hipMemcpyHostToDevice));
 }
 }  // namespace
 
@@ -1044,16 +815,10 @@ int tpsrhs_set_forcing(tpsrhs_handle h, const tpsrhs_forcing *in) {
   return guarded([&] {
     ForcingDev f = {};
     f.joule = h->forcing.joule;
-    // plane-node lists and sum buffers of the mixed-out zones of THIS call; they replace the previous call's, which
-    // are freed once the new block is in place (or these, if the call fails: the old forcing then stays as it was)
-    std::vector<void *> fresh;
-    struct Guard {
-      std::vector<void *> &v;
-      bool keep = false;
-      ~Guard() {
-        if (!keep) free_mixed_out(v);
-      }
-    } guard{fresh};
+    // plane-node lists and sum buffers of the mixed-out zones of THIS call; swapped with the previous call's once the new
+    // block is in place, so that whichever set is no longer in force is freed at the end of this scope (these, if the
+    // call fails: the old forcing then stays as it was)
+    std::vector<DevBuf<void>> mixed_out;
     if (in) {
       if (in->num_heat_sources < 0 || in->num_heat_sources > TPSRHS_MAXHEATSOURCES || in->num_sponge_zones < 0 ||
           in->num_sponge_zones > TPSRHS_MAXSPONGEZONES)
@@ -1150,12 +915,12 @@ int tpsrhs_set_forcing(tpsrhs_handle h, const tpsrhs_forcing *in) {
             throw std::invalid_argument("tpsrhs_set_forcing: a mixed-out sponge zone on a partitioned mesh needs runtime.reduce");
           d.mixed_out = 1;
           d.n_plane = static_cast<int>(nodes.size());
-          int *dn = dev_upload(nodes);
-          double *ds = dev_alloc<double>(TPSRHS_MAXEQUATIONS + 1);
-          fresh.push_back(dn);
-          fresh.push_back(ds);
-          d.plane_nodes = dn;
-          d.msum = ds;
+          DevBuf<int> dn(nodes);
+          DevBuf<double> ds(TPSRHS_MAXEQUATIONS + 1);
+          d.plane_nodes = dn.get();
+          d.msum = ds.get();
+          mixed_out.emplace_back(std::move(dn));
+          mixed_out.emplace_back(std::move(ds));
           for (int eq = 0; eq < TPSRHS_MAXEQUATIONS; eq++) d.target[eq] = 0.0;
         } else {
           if (s.solution_type != TPSRHS_SPONGE_USERDEF) throw std::invalid_argument("tpsrhs_set_forcing: unknown sponge solution type");
@@ -1165,8 +930,7 @@ int tpsrhs_set_forcing(tpsrhs_handle h, const tpsrhs_forcing *in) {
       }
     }
     // the device block first; the host copy, the buffers of the mixed-out zones and the configuration epoch are committed
-    // only once it is in place -- if the upload fails the operator keeps its previous forcing and the new buffers are
-    // released (the guard), the previous ones are not
+    // only once it is in place -- if the upload fails the operator keeps its previous forcing and its buffers
     const ForcingDev prev = h->forcing;
     const bool prev_active = h->forcing_active;
     h->forcing = f;
@@ -1178,12 +942,8 @@ int tpsrhs_set_forcing(tpsrhs_handle h, const tpsrhs_forcing *in) {
       h->forcing_active = prev_active;
       throw;
     }
-    std::vector<void *> old;
-    old.swap(h->d_mixed_out);
-    h->d_mixed_out = fresh;
-    guard.keep = true;
+    h->d_mixed_out.swap(mixed_out);
     h->config_epoch++;
-    free_mixed_out(old);
   });
 }
 
@@ -1231,14 +991,14 @@ int tpsrhs_update_gradients(tpsrhs_handle h, const double *x) {
 int tpsrhs_get_primitives(tpsrhs_handle h, double *up_out) {
   if (!h || !up_out) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_get_primitives: NULL argument");
   return guarded([&] {
-    HIP_CHECK(hipMemcpyAsync(up_out, h->d_Up, sizeof(double) * h->neq * h->ndofs, hipMemcpyDeviceToDevice, h->stream));
+    HIP_CHECK(hipMemcpyAsync(up_out, h->d_Up.get(), sizeof(double) * h->neq * h->ndofs, hipMemcpyDeviceToDevice, h->stream));
   });
 }
 
 int tpsrhs_get_gradients(tpsrhs_handle h, double *gradup_out) {
   if (!h || !gradup_out) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_get_gradients: NULL argument");
   return guarded([&] {
-    HIP_CHECK(hipMemcpyAsync(gradup_out, h->d_gradUp, sizeof(double) * h->dim * h->neq * h->ndofs,
+    HIP_CHECK(hipMemcpyAsync(gradup_out, h->d_gradUp.get(), sizeof(double) * h->dim * h->neq * h->ndofs,
                              hipMemcpyDeviceToDevice, h->stream));
   });
 }
@@ -1423,21 +1183,21 @@ void rk_stage(tpsrhs_operator *h, int64_t n, int64_t clamp_lo, int64_t clamp_hi,
   const int grid = static_cast<int>(std::min<int64_t>((items + 255) / 256, 8192));  // the grid cap of k_rk4_stage
   if (vec)
     hipLaunchKernelGGL((k_rk_stage<OP, true, 256>), dim3(grid), dim3(256), 0, h->stream, n, clamp_lo, clamp_hi, dt, dt_dev, x, k, y,
-                       h->d_nan);
+                       h->d_nan.get());
   else
     hipLaunchKernelGGL((k_rk_stage<OP, false, 256>), dim3(grid), dim3(256), 0, h->stream, n, clamp_lo, clamp_hi, dt, dt_dev, x, k, y,
-                       h->d_nan);
+                       h->d_nan.get());
   HIP_CHECK(hipGetLastError());
 }
 
 void rk_stages(tpsrhs_operator *h, int integrator, double *x, double dt, const double *dt_dev) {
   const int64_t n = static_cast<int64_t>(h->neq) * h->ndofs;
   if (!h->d_rk) {
-    h->d_rk = dev_alloc<double>(3 * n);
-    h->d_nan = dev_alloc<unsigned long long>(1);
-    HIP_CHECK(hipMemsetAsync(h->d_nan, 0, sizeof(unsigned long long), h->stream));
+    h->d_rk = DevBuf<double>(3 * n);
+    h->d_nan = DevBuf<unsigned long long>(1);
+    HIP_CHECK(hipMemsetAsync(h->d_nan.get(), 0, sizeof(unsigned long long), h->stream));
   }
-  double *k = h->d_rk, *y = k + ((n + 1) & ~static_cast<int64_t>(1));  // y ends at or before 2 n + 1 <= 3 n
+  double *k = h->d_rk.get(), *y = k + ((n + 1) & ~static_cast<int64_t>(1));  // y ends at or before 2 n + 1 <= 3 n
   h->ta_valid = false;  // every Mult of these schemes runs its own k_traces sweep
   const bool mixture = h->phys.working_fluid == TPSRHS_USER_DEFINED;
   const int sp_first = h->nvel + 2;
@@ -1700,7 +1460,7 @@ void probe_record(tpsrhs_operator *h, const double *x) {
   if (r < 0) return;
   const int64_t per = static_cast<int64_t>(h->neq) * log.sampler->npts;
   sample_field(h, log.sampler, h->neq, x, log.d_values.get() + r * per);
-  HIP_CHECK(hipMemcpyAsync(log.d_times.get() + r, h->d_ctl + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  HIP_CHECK(hipMemcpyAsync(log.d_times.get() + r, h->d_ctl.get() + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
 }
 
 // the position of s among the samplers of ss, or their end
@@ -1777,7 +1537,7 @@ void launch_locate(tpsrhs_operator *h, tpsrhs_sampler *s, const double *xyz, dou
   const LocateGridView<DIM> g = device_grid<DIM>(h, tol);
   HIP_CHECK(hipMemsetAsync(s->d_nfound.get(), 0, sizeof(unsigned long long), h->stream));
   if (grid == 0) return;
-  hipLaunchKernelGGL((k_locate<DIM, BLOCK>), dim3(static_cast<unsigned>(grid)), dim3(BLOCK), 0, h->stream, g, h->d_verts, s->npts,
+  hipLaunchKernelGGL((k_locate<DIM, BLOCK>), dim3(static_cast<unsigned>(grid)), dim3(BLOCK), 0, h->stream, g, h->d_verts.get(), s->npts,
                      xyz, tol, s->d_elem.get(), s->d_ref.get(), s->d_perm.get(), s->d_nfound.get());
   HIP_CHECK(hipGetLastError());
 }
@@ -1814,10 +1574,10 @@ void node_coordinates_device(tpsrhs_operator *h, double *xyz_out, hipStream_t st
   if (grid >= (int64_t(1) << 31)) throw Unsupported("tpsrhs_node_coordinates: more than 2^39 nodes");
   if (h->dim == 2)
     hipLaunchKernelGGL((k_node_coordinates<2, BLOCK>), dim3(static_cast<unsigned>(grid)), dim3(BLOCK), 0, stream, h->ndofs,
-                       h->order + 1, nodes, h->d_verts, xyz_out);
+                       h->order + 1, nodes, h->d_verts.get(), xyz_out);
   else
     hipLaunchKernelGGL((k_node_coordinates<3, BLOCK>), dim3(static_cast<unsigned>(grid)), dim3(BLOCK), 0, stream, h->ndofs,
-                       h->order + 1, nodes, h->d_verts, xyz_out);
+                       h->order + 1, nodes, h->d_verts.get(), xyz_out);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -2012,7 +1772,7 @@ int tpsrhs_probe_configure(tpsrhs_handle h, tpsrhs_sampler_handle s, int64_t int
     log.index.capacity = capacity;
     log.d_values = DevBuf<double>(capacity * h->neq * s->npts);
     log.d_times = DevBuf<double>(capacity);
-    if (!h->d_ctl) h->d_ctl = dev_alloc<double>(3);  // the loop's {dt, time, max speed}: a record copies the time from there
+    if (!h->d_ctl) h->d_ctl = DevBuf<double>(3);  // the loop's {dt, time, max speed}: a record copies the time from there
     // complete: a call that throws above leaves the probes off.  (h->sampling exists: s is one of its samplers)
     h->sampling->probe = std::move(log);
   });
@@ -2054,10 +1814,10 @@ void launch_wall_distance(tpsrhs_operator *h, int64_t nfaces, const double *face
   const DevBuf<double> table(coef);
   const dim3 g(static_cast<unsigned>(grid)), b(WD_BLOCK);
   if (cull)
-    hipLaunchKernelGGL((k_wall_distance<DIM, true>), g, b, 0, h->stream, h->ndofs, h->order + 1, nodes, h->d_verts, nfaces,
+    hipLaunchKernelGGL((k_wall_distance<DIM, true>), g, b, 0, h->stream, h->ndofs, h->order + 1, nodes, h->d_verts.get(), nfaces,
                        table.get(), out);
   else
-    hipLaunchKernelGGL((k_wall_distance<DIM, false>), g, b, 0, h->stream, h->ndofs, h->order + 1, nodes, h->d_verts, nfaces,
+    hipLaunchKernelGGL((k_wall_distance<DIM, false>), g, b, 0, h->stream, h->ndofs, h->order + 1, nodes, h->d_verts.get(), nfaces,
                        table.get(), out);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(h->stream));  // the table is freed on return
@@ -2143,7 +1903,7 @@ void launch_integrate(tpsrhs_operator *h, const tpsrhs_integrals_state *is, cons
                       const double *exact, int radial, double *partial) {
   typedef IntegCfg<DIM, P> C;
   hipLaunchKernelGGL((k_integrate<DIM, P>), dim3(is->integ_blocks), dim3(64), 0, h->stream, h->ne, is->integ_run, nrows, h->ndofs,
-                     static_cast<int64_t>(h->ne) * C::NQD, radial, tab, h->d_verts, field, exact, partial);
+                     static_cast<int64_t>(h->ne) * C::NQD, radial, tab, h->d_verts.get(), field, exact, partial);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -2203,8 +1963,8 @@ void monitor_record(tpsrhs_operator *h, const double *x) {
   integrate_field(h, h->neq, x, nullptr, axisym, log.d_totals.get() + r * h->neq, nullptr);
   nodal_stats_field(h, h->neq, x, log.d_mins.get() + r * h->neq, log.d_maxs.get() + r * h->neq, nullptr);
   // {dt of the next step, time}: the loop's control block, which the variable-dt loop never has on the host
-  HIP_CHECK(hipMemcpyAsync(log.d_dts.get() + r, h->d_ctl, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  HIP_CHECK(hipMemcpyAsync(log.d_times.get() + r, h->d_ctl + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  HIP_CHECK(hipMemcpyAsync(log.d_dts.get() + r, h->d_ctl.get(), sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  HIP_CHECK(hipMemcpyAsync(log.d_times.get() + r, h->d_ctl.get() + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
 }
 }  // namespace
 
@@ -2254,7 +2014,7 @@ int tpsrhs_monitor_configure(tpsrhs_handle h, int64_t interval, int64_t capacity
     log.d_totals = DevBuf<double>(capacity * h->neq);
     log.d_mins = DevBuf<double>(capacity * h->neq);
     log.d_maxs = DevBuf<double>(capacity * h->neq);
-    if (!h->d_ctl) h->d_ctl = dev_alloc<double>(3);  // the loop's {dt, time, max speed}: a record copies from there
+    if (!h->d_ctl) h->d_ctl = DevBuf<double>(3);  // the loop's {dt, time, max speed}: a record copies from there
     is->monitor = std::move(log);  // complete: a call that throws above leaves the monitor off
   });
 }
