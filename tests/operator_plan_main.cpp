@@ -208,9 +208,9 @@ void print_plan(const Row &row) {
   using namespace tpsrhs;
   try {
     const OperatorPlan p = plan_operator(row.dim, row.disc, row.phys, static_cast<int>(row.bcs.size()), row.bcs.data());
-    std::printf("%s: plan nc %d dim %d order %d nvel %d neq %d plasma %d lte %d heavy2d %d les %d any_nr %d sponge %d "
+    std::printf("%s: plan nc %d dim %d order %d nvel %d neq %d sp %d %d plasma %d lte %d heavy2d %d les %d any_nr %d sponge %d "
                 "n %.17g %.17g %.17g p %.17g %.17g %.17g width %.17g ratio %.17g sgs_const %.17g transport %d unit %s\n",
-                row.name.c_str(), p.nc, p.dim, p.order, p.nvel, p.neq, p.plasma, p.lte, p.heavy2d, p.les, p.any_nr, p.sponge,
+                row.name.c_str(), p.nc, p.dim, p.order, p.nvel, p.neq, p.sp_first, p.sp_last, p.plasma, p.lte, p.heavy2d, p.les, p.any_nr, p.sponge,
                 p.sponge_n[0], p.sponge_n[1], p.sponge_n[2], p.sponge_p[0], p.sponge_p[1], p.sponge_p[2], p.sponge_width,
                 p.sponge_ratio, p.sgs_const, p.transport, p.unit.empty() ? "-" : p.unit.c_str());
   } catch (const Unsupported &e) {

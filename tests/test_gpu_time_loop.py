@@ -4,8 +4,8 @@ to x by the caller, in the orders a driver makes them.
 The loop keeps state between stages, steps and calls, and every piece of it is a cache that can go stale without
 producing a NaN:
   - k_flux's epilogue forms the next stage's face-node traces (RkDev::ta_out, kernels.hpp); inside advance stage 4 hands
-    them to the next step (ta_valid / ta_chain, operator.hpp launch_all);
-  - advance captures one step into a hipGraph and replays it, also in later calls whose StepKey matches (tpsrhs.hip);
+    them to the next step (TraceChain, trace_chain.hpp; launch_all asks it what each Mult reads and writes);
+  - advance captures one step into a hipGraph and replays it, also in later calls whose StepKey matches (StepGraph);
   - consecutive sweeps alternate their direction (sweep_parity); a captured graph keeps the one it was captured with.
 
 Every scenario makes the same calls three times:
@@ -18,22 +18,10 @@ fused and plain must agree bit for bit after EVERY call (state, Mult result, tim
 where the numbers come from, never the numbers.  Both must match the oracle: dry air within the bound of
 test_gpu_rk4.py (rel_maxnorm < 1e-13), the plasma within _plasma_bound below.
 
-Why StepKey = (x, constant_dt, bstate_cur, config_epoch, cfl hmin / dim) is enough -- what else could change what a
-replayed step launches, and why it cannot:
-  - ta_chain is !forcing_active, and forcing_active changes only in tpsrhs_set_forcing / tpsrhs_set_joule_heating, which
-    bump config_epoch (test_calls_between_advances[forcing] crosses it both ways).
-  - ta_valid and the trace buffers: the first step of every advance call runs outside the graph with ta_valid = false
-    (a k_traces sweep of its own), and the four stages of a step swap d_TA / d_TA2 an even number of times, so the
-    captured step and every step it is replayed as start by reading d_TA and end by writing d_TA.  fuse_traces is fixed
-    when the operator is created.
-  - sweep_parity: only the order in which the workgroups walk the block list.  Every element's outputs depend on the
-    buffers of the previous sweep only, and the reductions over blocks (max char speed, NaN census) are a max and an
-    integer sum, so the direction cannot change a number (test_calls_between_advances[mult]: one Mult flips the parity,
-    and the next advance replays the graph captured with the other one).
-  - bstate_init: false only until the first Mult of an operator with non-reflecting faces.  The first step of every
-    advance runs outside the graph, so every captured step has it true, and nothing sets it back.
-  - nr_dt, which the dry-air parameter block carries by value: inside advance the boundary kernels read dt from device
-    memory (nr_dt_dev = d_ctl), never the block's copy.
+Why StepKey is enough to decide a replay, and why the trace buffers swap an even number of times per step, is argued at
+the top of tps_amd/csrc/trace_chain.hpp, next to the state it is about; tests/test_trace_chain.py drives that state
+machine on the host.  The scenarios here cross each point of the argument on the device: test_calls_between_advances[forcing]
+crosses config_epoch both ways, [mult] flips the sweep parity under a captured graph.
 """
 import numpy as np
 import pytest
@@ -279,7 +267,7 @@ BETWEEN = {
     "mult": [("mult",)],  # an odd number of sweeps: the next advance replays a graph of the other sweep direction
     "rk4_step": [("rk4_step",)],
     "outside_write": [("touch",)],
-    # config_epoch twice: ta_chain off (the separate stage kernel) and on again, a graph captured each time
+    # config_epoch twice: chaining off (the separate stage kernel) and on again, a graph captured each time
     "forcing": [("forcing", PRESSURE_GRADIENT), ("advance", 4, False), ("forcing", capi.make_forcing())],
     "new_tensor": [("new_tensor",)],  # a new StepKey.x
 }

@@ -6,6 +6,8 @@ and the messages of the library:
 
     nvel = 3 for the axisymmetric formulation, else dim;  neq = nvel + 2 for dry air and the table gas
     mixtures: neq = nvel + 2 + (species - 2 if ambipolar else species - 1) + (1 if two temperatures)
+    sp: the species rows [first, last) of the state that the time loop clamps at zero (Check_Undershoot): they follow the
+        nvel + 2 flow rows, species - 2 of them if ambipolar else species - 1; empty (first = last) for dry air and the table gas
     kernel family of a mixture: plasma_<3d | 2d | axi>_n<species>[a if ambipolar][_hi for orders 4 and 5 of the Gauss-Legendre pair]
     heavy2d: the 2-D kernels of mixtures and of the axisymmetric formulation;  les: dry air with a model or a sponge
     sponge plane: normal / |normal| over the first dim components, the others 0; width = ratio = 1 without a sponge
@@ -41,7 +43,7 @@ ORDER = "polynomial order %d is not built (1..5)"
 P2 = (0.25, -0.5, 0.0)  # the sponge point of the program, first two components (2-D)
 
 # name -> (class, message) of a refusal, or the plan's fields that differ from a plain dry-air plan of that dim and order
-# (nc 0, nvel = dim, neq = dim + 2, every flag 0, no sponge: n = p = 0, width = ratio = 1, sgs_const 0, transport 0, no unit)
+# (nc 0, nvel = dim, neq = dim + 2, sp = (nvel + 2, nvel + 2), every flag 0, no sponge: n = p = 0, width = ratio = 1, sgs_const 0, transport 0, no unit)
 ROWS = [
     ("dry3d_gl", dict(dim=3, order=2)),
     ("dry2d_gl", dict(dim=2, order=5)),
@@ -68,7 +70,7 @@ ROWS = [
     ("order_6_mixture", (U, ORDER % 6)),
     ("dry_16_bcs", dict(dim=3, order=2)),
     ("dry_17_bcs", (U, "too many boundary conditions")),
-    ("mixture_8_bcs", dict(dim=3, order=2, plasma=1, neq=6, transport=1, unit="plasma_3d_n3a")),
+    ("mixture_8_bcs", dict(dim=3, order=2, plasma=1, neq=6, sp=(5, 6), transport=1, unit="plasma_3d_n3a")),
     ("mixture_9_bcs", (U, "too many boundary conditions")),
     ("reflecting_set", dict(dim=3, order=2)),
     ("nr_outlet", dict(dim=3, order=2, any_nr=1)),
@@ -105,6 +107,7 @@ def _general_wall_rows():
                         want = (I, "viscous_general wall: plasma must be ambipolar for the sheath condition")
                     else:
                         want = dict(dim=2, order=2, plasma=1, heavy2d=1, neq=2 + 2 + (1 if ambi else 2) + two_t,
+                                    sp=(4, 5 if ambi else 6),
                                     unit="plasma_2d_n3a" if ambi else "plasma_2d_n3")
                     rows.append((name, want))
     return rows
@@ -112,17 +115,17 @@ def _general_wall_rows():
 
 ROWS += _general_wall_rows()
 ROWS += [
-    ("ternary_3d_p3", dict(dim=3, order=3, plasma=1, neq=6, transport=1, unit="plasma_3d_n3a")),
-    ("ternary_3d_p4", dict(dim=3, order=4, plasma=1, neq=6, transport=1, unit="plasma_3d_n3a_hi")),
-    ("ternary_3d_gll_p3", dict(dim=3, order=3, nc=1, plasma=1, neq=6, transport=1, unit="plasma_3d_n3a")),
-    ("ternary_2d_not_ambipolar_2t", dict(dim=2, order=2, plasma=1, heavy2d=1, neq=7, unit="plasma_2d_n3")),
-    ("seven_axi_p3", dict(dim=2, order=3, nvel=3, plasma=1, heavy2d=1, neq=11, transport=2, unit="plasma_axi_n7a")),
-    ("seven_axi_p4", dict(dim=2, order=4, nvel=3, plasma=1, heavy2d=1, neq=11, transport=2, unit="plasma_axi_n7a_hi")),
-    ("seven_3d_not_ambipolar_p5", dict(dim=3, order=5, plasma=1, neq=11, transport=2, unit="plasma_3d_n7_hi")),
-    ("eight_constant", dict(dim=3, order=2, plasma=1, neq=11, unit="plasma_3d_n8a")),
+    ("ternary_3d_p3", dict(dim=3, order=3, plasma=1, neq=6, sp=(5, 6), transport=1, unit="plasma_3d_n3a")),
+    ("ternary_3d_p4", dict(dim=3, order=4, plasma=1, neq=6, sp=(5, 6), transport=1, unit="plasma_3d_n3a_hi")),
+    ("ternary_3d_gll_p3", dict(dim=3, order=3, nc=1, plasma=1, neq=6, sp=(5, 6), transport=1, unit="plasma_3d_n3a")),
+    ("ternary_2d_not_ambipolar_2t", dict(dim=2, order=2, plasma=1, heavy2d=1, neq=7, sp=(4, 6), unit="plasma_2d_n3")),
+    ("seven_axi_p3", dict(dim=2, order=3, nvel=3, plasma=1, heavy2d=1, neq=11, sp=(5, 10), transport=2, unit="plasma_axi_n7a")),
+    ("seven_axi_p4", dict(dim=2, order=4, nvel=3, plasma=1, heavy2d=1, neq=11, sp=(5, 10), transport=2, unit="plasma_axi_n7a_hi")),
+    ("seven_3d_not_ambipolar_p5", dict(dim=3, order=5, plasma=1, neq=11, sp=(5, 11), transport=2, unit="plasma_3d_n7_hi")),
+    ("eight_constant", dict(dim=3, order=2, plasma=1, neq=11, sp=(5, 11), unit="plasma_3d_n8a")),
     ("eight_argon_mixture", (U, "argon_mixture transport supports at most 7 species (Ar, Ar.+1, Ar_m, Ar_r, Ar_p, Ar_h, E)")),
     ("four_argon_minimal", (U, "argon_minimal transport is the ternary (Ar, Ar.+1, E) model")),
-    ("four_argon_mixture", dict(dim=2, order=1, plasma=1, heavy2d=1, neq=6, transport=2, unit="plasma_2d_n4a")),
+    ("four_argon_mixture", dict(dim=2, order=1, plasma=1, heavy2d=1, neq=6, sp=(4, 6), transport=2, unit="plasma_2d_n4a")),
     ("two_species", (U, SPECIES)),
     ("nine_species", (U, SPECIES)),
     ("lte_transport_for_a_mixture", (U, "transport model outside the built scope (constant, argon_minimal, argon_mixture)")),
@@ -142,7 +145,7 @@ ROWS += [
                                  ratio=8.0, sgs_const=0.135)),
     ("sponge_dry_zero_width", (I, WIDTH)),
     ("sponge_dry_2d_normal_in_z_only", (I, NORMAL)),
-    ("sponge_mixture_2d", dict(dim=2, order=2, plasma=1, heavy2d=1, neq=5, transport=1, unit="plasma_2d_n3a", sponge=1,
+    ("sponge_mixture_2d", dict(dim=2, order=2, plasma=1, heavy2d=1, neq=5, sp=(4, 5), transport=1, unit="plasma_2d_n3a", sponge=1,
                                n=(0.0, 1.0, 0.0), p=P2, width=0.2, ratio=11.0)),
     ("sponge_dry_axi", dict(dim=2, order=2, nvel=3, neq=5, heavy2d=1, sponge=1, n=(4.0 / 5.0, 3.0 / 5.0, 0.0), p=P2, width=0.5, ratio=2.0)),
     ("sponge_lte", dict(dim=2, order=2, nvel=3, neq=5, heavy2d=1, lte=1, sponge=1, n=(1.0, 0.0, 0.0), p=P2, width=0.5, ratio=2.0)),
@@ -167,8 +170,8 @@ def _plan_fields(line):
     assert f[0] == "plan", line
     v, k = {}, 1
     while k < len(f):
-        width = 3 if f[k] in ("n", "p") else 1
-        v[f[k]] = tuple(f[k + 1:k + 1 + width]) if width == 3 else f[k + 1]
+        width = 3 if f[k] in ("n", "p") else (2 if f[k] == "sp" else 1)
+        v[f[k]] = tuple(f[k + 1:k + 1 + width]) if width > 1 else f[k + 1]
         k += 1 + width
     return v
 
@@ -190,7 +193,9 @@ def _check(exe):
         accepted += 1
         v = _plan_fields(rest)
         dim = want["dim"]
-        full = dict(nc=0, nvel=dim, neq=want.get("nvel", dim) + 2, plasma=0, lte=0, heavy2d=0, les=0, any_nr=0, sponge=0,
+        rows = want.get("nvel", dim) + 2
+        assert ("sp" in want) == bool(want.get("plasma")), name  # every mixture's species rows are written out above
+        full = dict(nc=0, nvel=dim, neq=rows, sp=(rows, rows), plasma=0, lte=0, heavy2d=0, les=0, any_nr=0, sponge=0,
                     n=(0.0, 0.0, 0.0), p=(0.0, 0.0, 0.0), width=1.0, ratio=1.0, sgs_const=0.0, transport=0, unit="-")
         full.update(want)
         assert set(v) == set(full), line

@@ -6,7 +6,10 @@ times the steps inside ONE advance call instead (tpsrhs_advance / tpsrhs_advance
 captured step graph), with the running statistics sampled every K steps (0: off), and one add_sample on its own.
     python tools/rk4_time.py --advance --probe-interval 1 --monitor-interval 1 ...
 adds a probe record (8 points) and / or a monitor record every K steps, with room for every record: at K = 1 the
-between-step hooks run after every step, the case where their host side shows."""
+between-step hooks run after every step, the case where their host side shows.
+    python tools/rk4_time.py --mesh 4 12 3 ...
+takes the O-grid cylinder with that many cells (radial, around, spanwise) instead of 28 x 112 x 16: on a small mesh a step
+is bound by its launches, and the host side of the loop shows (TPSRHS_GRAPH=0: the plain launch loop)."""
 import argparse
 import os
 import sys
@@ -24,6 +27,7 @@ ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
 ap.add_argument("--integrator", default="rk4", choices=sorted(set(capi.INTEGRATORS) - {"rk6"}))
 ap.add_argument("--workload", default="cfg2", help="cfg2 (BASELINE configs[1]) or a workload of bench.py, e.g. argon_p3")
 ap.add_argument("--steps", type=int, default=20)
+ap.add_argument("--mesh", type=int, nargs=3, default=[28, 112, 16], metavar=("NR", "NTHETA", "NZ"), help="cells of the O-grid cylinder")
 ap.add_argument("--dt", type=float, default=None, help="default: 1e-7 (cfg2), 1e-10 (the others: stiff chemistry)")
 ap.add_argument("--advance", action="store_true", help="time the steps of one advance call (the device loop)")
 ap.add_argument("--stats-interval", type=int, default=0, help="--advance: sample the running statistics every K steps")
@@ -36,14 +40,14 @@ side = torch.cuda.Stream() if args.advance else None  # a capturable stream: adv
 if side is not None:
     torch.cuda.set_stream(side)
 if args.workload == "cfg2":
-    c = cases.config(2)
+    c = cases.cyl3d(*args.mesh, 3, capi.NS)  # the default mesh: cases.config(2)
     op = RHSoperator(c.mesh, c.disc, c.physics, c.bcs, stream=side)
     U, dt = c.state(), 1e-7
 else:
     import bench  # noqa: E402
 
     order, physics, make_bcs, make_state, _, _ = bench.workload(args.workload)
-    mesh = meshgen.ogrid_cylinder_slab(28, 112, 16, 0, 1)
+    mesh = meshgen.ogrid_cylinder_slab(*args.mesh, 0, 1)
     U, dt = make_state(node_coordinates(mesh, order), physics), 1e-10
     op = RHSoperator(mesh, capi.Disc(order, 0, 0, 0, 0), physics, make_bcs(physics), stream=side)
 if args.dt is not None:

@@ -19,6 +19,7 @@
 #include "device_buffer.hpp"
 #include "kernels.hpp"
 #include "topology.hpp"
+#include "trace_chain.hpp"
 #include "unsupported.hpp"
 
 using namespace tpsrhs;
@@ -33,6 +34,46 @@ const char *kKernelNames[NKERN] = {"k_traces", "k_gradient", "k_flux"};
 struct tpsrhs_stats_state;  // statistics.hpp: running mean and velocity covariances (tpsrhs.hip only)
 struct tpsrhs_sampling_state;  // sampling.hpp: point samplers and probe records (tpsrhs.hip only)
 struct tpsrhs_integrals_state;  // integrals.hpp: reduction scratch and monitor records (tpsrhs.hip only)
+
+// One step (or pair of steps, steps_per_graph) of tpsrhs_advance / tpsrhs_advance_with as an executable graph: dt lives in
+// device memory, so the step replays as is.  Owns the executable as DevBuf owns memory; whoever destroys it does so on the
+// device that holds it.
+class StepGraph {
+ public:
+  StepGraph() = default;
+  StepGraph(const StepGraph &) = delete;
+  StepGraph &operator=(const StepGraph &) = delete;
+  ~StepGraph() { reset(); }
+  // the graph for `key`: the one at hand, or what `capture` enqueues on `stream`, captured and instantiated in its place
+  template <class F>
+  void ensure(const StepKey &key, hipStream_t stream, F &&capture) {
+    if (exec_ && key_ == key) return;
+    reset();
+    hipGraph_t g = nullptr;
+    HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+    try {
+      capture();
+    } catch (...) {
+      (void)hipStreamEndCapture(stream, &g);
+      if (g) (void)hipGraphDestroy(g);
+      throw;
+    }
+    HIP_CHECK(hipStreamEndCapture(stream, &g));
+    const hipError_t ie = hipGraphInstantiate(&exec_, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    HIP_CHECK(ie);
+    key_ = key;
+  }
+  void launch(hipStream_t stream) { HIP_CHECK(hipGraphLaunch(exec_, stream)); }
+
+ private:
+  void reset() {
+    if (exec_) (void)hipGraphExecDestroy(exec_);
+    exec_ = nullptr;
+  }
+  hipGraphExec_t exec_ = nullptr;
+  StepKey key_;
+};
 
 struct tpsrhs_operator {
   int dim = 0, order = 0, neq = 0, nvel = 0;
@@ -53,12 +94,13 @@ struct tpsrhs_operator {
   DevBuf<double> d_verts;
   DevBuf<int2> d_face_info;
   DevBuf<double> d_Up, d_gradUp, d_TA, d_TB;
+  // buffer 1 of loop.chain (d_TA is 0), allocated by the first hand-over: k_flux forms the next stage's traces in its epilogue.
+  // Single-rank 3-D collocated kernels only (flux_fuses_traces); TPSRHS_FUSE_TRACES=0 keeps the separate sweep.
+  DevBuf<double> d_TA2;
   DevBuf<double> d_speed, d_block_speed;
   int flux_grid = 0;
   DevBuf<double> d_xh, d_yh;  // staging for tpsrhs_mult_host
-  DevBuf<double> d_rk;        // k | y | z of tpsrhs_rk4_step
-  DevBuf<unsigned long long> d_nan;
-  RkDev rk = {};  // mode 0 outside tpsrhs_rk4_step / tpsrhs_advance: k_flux writes the residual
+  RkDev rk = {};  // a stage's block is in force for its own launch only (rk4_stages); mode 0: k_flux writes the residual
   MixLenDev mixlen = {nullptr, 0.0, 1.0, 0.0};  // MixingLengthTransport (tpsrhs_set_mixing_length); distance NULL: off
   ForcingDev forcing = {};                  // host copy of the optional forcing terms (tpsrhs_set_forcing / _joule_heating)
   DevBuf<ForcingDev> d_forcing;
@@ -74,24 +116,22 @@ struct tpsrhs_operator {
   bool bstate_init = false;
   DevBuf<double> d_bc_sums;
   double nr_dt = 0.0;
-  DevBuf<double> d_ctl;             // {dt, time, max speed} of tpsrhs_advance
   const double *nr_dt_dev = nullptr;  // non-NULL while tpsrhs_advance runs: the boundary conditions read dt there
   tpsrhs_reduce_fn reduce = nullptr;
   void *reduce_ctx = nullptr;
-  // one step of tpsrhs_advance / tpsrhs_advance_with as an executable graph (dt lives in device memory, so the step
-  // replays as is); the key holds the integrator: a step captured for one scheme is never replayed for another
-  hipGraphExec_t step_graph = nullptr;
-  struct StepKey {
-    const void *x = nullptr;
-    int constant_dt = 0, bstate_cur = 0, epoch = 0;
-    int integrator = TPSRHS_RK4;
-    double coef = 0.0;
-    bool operator==(const StepKey &o) const {
-      return x == o.x && constant_dt == o.constant_dt && bstate_cur == o.bstate_cur && epoch == o.epoch &&
-             integrator == o.integrator && coef == o.coef;
-    }
-  } step_key;
-  int config_epoch = 0;  // bumped by everything that changes what a step launches (forcing terms, ...)
+  // The device time loop (tpsrhs_step / _rk4_step / _advance / _advance_with): what it keeps between stages, steps and
+  // calls.  The rules are in trace_chain.hpp.
+  struct TimeLoop {
+    DevBuf<double> d_rk;               // k | y | z of the stages; stage_scratch (tpsrhs.hip) allocates both at the first step
+    DevBuf<unsigned long long> d_nan;  // the NaN census: zeroed by step_with / advance_with per call, counted by the stages
+    int sp_first = 0, sp_last = 0;     // the species rows Check_Undershoot clamps; setup, from the plan
+    DevBuf<double> d_ctl;              // {dt, time, max speed}: loop_ctl allocates, advance_with and k_step_end write
+    StepGraph graph;                   // advance_with, through ensure
+    TraceChain chain;                  // launch_all asks mult(); rk4_stages, rk_stages and advance_with make the transitions
+    int config_epoch = 0;              // bumped by whatever changes what a step launches: the forcing and mixing-length setters
+    bool sweep_alt = true;             // alternate the direction of consecutive sweeps (launch_all); setup, TPSRHS_SWEEP_ALT
+    int sweep_parity = 0;              // launch_all flips it once per Mult
+  } loop;
   // halo
   tpsrhs_halo_fn halo = nullptr;
   void *halo_ctx = nullptr;
@@ -113,16 +153,6 @@ struct tpsrhs_operator {
 
   void (*launch)(tpsrhs_operator *, const double *, double *, bool) = nullptr;
   void (*point_eval)(tpsrhs_operator *, int, int64_t, const double *, double *) = nullptr;
-  // Time loop: k_flux of stages 1..3 forms the next stage's face-node traces in its epilogue (RkDev::ta_out, kernels.hpp),
-  // alternating between d_TA and d_TA2; the next stage then starts at k_gradient.  Single-rank 3-D collocated kernels only
-  // (flux_fuses_traces); TPSRHS_FUSE_TRACES=0 keeps the separate sweep.
-  bool fuse_traces = true;
-  bool ta_valid = false;     // d_ta_next holds the traces of the input of the stage that runs next
-  bool ta_chain = false;     // inside tpsrhs_advance: stage 4 leaves the traces of the new solution for the next step
-  DevBuf<double> d_TA2;
-  double *d_ta_next = nullptr;  // d_TA or d_TA2
-  bool sweep_alt = true;  // alternate the direction of consecutive sweeps (launch_all); TPSRHS_SWEEP_ALT
-  int sweep_parity = 0;
   VsDev vs2d = {};  // viscous sponge of the 2-D heavy kernels (MeshDev::vs); enabled = 0: none
   // tpsrhs_stats_configure / tpsrhs_sampler_create, tpsrhs_probe_configure / tpsrhs_integrate, tpsrhs_monitor_configure;
   // NULL: none yet.  Created, used and released (tpsrhs_destroy) by tpsrhs.hip.  Raw pointers because their types are
@@ -150,7 +180,6 @@ struct tpsrhs_operator {
   // what is not memory; the buffers free themselves after this body, on the device set here
   ~tpsrhs_operator() {
     (void)hipSetDevice(device);
-    if (step_graph) (void)hipGraphExecDestroy(step_graph);
     for (auto &e : ev_halo)
       if (e) (void)hipEventDestroy(e);
     if (comm_stream) (void)hipStreamDestroy(comm_stream);
@@ -218,28 +247,14 @@ void launch_all(tpsrhs_operator *op, const double *x, double *y, bool gradients_
   // Alternating sweep direction (TPSRHS_SWEEP_ALT): k_traces and k_flux of a Mult walk the block list one way, k_gradient
   // the other, and the next Mult starts the other way round -- every sweep begins with what its predecessor wrote last
   // (xcd_block).  The direction is per sweep, the same for its halo and interior launches.
-  const int dir0 = op->sweep_alt ? op->sweep_parity : 0;
+  const int dir0 = op->loop.sweep_alt ? op->loop.sweep_parity : 0;
   // which trace buffer this Mult reads, whether its k_traces sweep is already done, and where k_flux puts the next one's
-  double *ta = op->d_TA.get();
-  bool have_traces = false;
-  if constexpr (flux_fuses_traces<C, PH>()) {
-    const int stage = op->rk.mode;
-    // the previous stage of this step left them (rk4_stages: its output is this input) -- or, inside tpsrhs_advance
-    // (ta_chain), the last stage of the previous step, whose output x is this step's input
-    if ((stage >= 2 || (stage == 1 && op->ta_chain)) && op->ta_valid) {
-      ta = op->d_ta_next;
-      have_traces = true;
-    }
-    op->ta_valid = false;
-    if (op->fuse_traces && !gradients_only && op->topo.num_shared == 0 && stage >= 1 && (stage <= 3 || op->ta_chain)) {
-      if (!op->d_TA2) op->d_TA2 = DevBuf<double>(static_cast<int64_t>(op->ne) * op->nfaces * 2 * PH::NEQ * C::NF);
-      op->rk.ta_out = (ta == op->d_TA.get()) ? op->d_TA2.get() : op->d_TA.get();
-      op->d_ta_next = op->rk.ta_out;
-      op->ta_valid = true;  // (cleared again below if a launch throws)
-    }
-  } else {
-    op->ta_valid = false;
-  }
+  const TraceChain::Mult tc = op->loop.chain.mult(flux_fuses_traces<C, PH>(), op->rk.mode, gradients_only, op->topo.num_shared > 0);
+  if (tc.write >= 0 && !op->d_TA2) op->d_TA2 = DevBuf<double>(static_cast<int64_t>(op->ne) * op->nfaces * 2 * PH::NEQ * C::NF);
+  double *const tbuf[2] = {op->d_TA.get(), op->d_TA2.get()};
+  double *const ta = tbuf[tc.read];
+  const bool have_traces = tc.have_traces;
+  if (tc.write >= 0) op->rk.ta_out = tbuf[tc.write];
   auto traces = [&](MeshDev m, int grid) {
     if (have_traces) return;
     m.reverse = dir0;
@@ -247,7 +262,7 @@ void launch_all(tpsrhs_operator *op, const double *x, double *y, bool gradients_
     HIP_CHECK(hipGetLastError());
   };
   auto gradient = [&](MeshDev m, int grid) {
-    m.reverse = op->sweep_alt ? 1 - dir0 : 0;
+    m.reverse = op->loop.sweep_alt ? 1 - dir0 : 0;
     hipLaunchKernelGGL((k_gradient<C, PH>), dim3(grid), dim3(C::BLOCK), 0, s, m, prm_k, x, ta, op->d_Up.get(), op->d_gradUp.get(),
                        op->d_TB.get());
     HIP_CHECK(hipGetLastError());
@@ -304,7 +319,7 @@ void launch_all(tpsrhs_operator *op, const double *x, double *y, bool gradients_
     HIP_CHECK(hipEventRecord(op->ev[0], s));
   }
   const MeshDev all = op->mesh_dev();
-  if (op->sweep_alt) op->sweep_parity ^= 1;  // (read into dir0 above: the next Mult starts from the other end)
+  if (op->loop.sweep_alt) op->loop.sweep_parity ^= 1;  // (read into dir0 above: the next Mult starts from the other end)
   if (op->topo.num_shared == 0) {
     traces(all, nblocks);
     if (op->timing) HIP_CHECK(hipEventRecord(op->ev[1], s));

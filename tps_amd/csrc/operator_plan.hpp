@@ -30,6 +30,7 @@ inline bool plan_is_non_reflecting(int category, int type) {
 struct OperatorPlan {
   int nc = 0;  // 1: the non-collocated Gauss-Lobatto pair, 0: the collocated Gauss-Legendre pair
   int dim = 0, order = 0, nvel = 0, neq = 0;
+  int sp_first = 0, sp_last = 0;  // the species rows [sp_first, sp_last) of the state, which Check_Undershoot clamps; empty without a mixture
   bool plasma = false, lte = false;  // the working fluid; neither: dry air
   bool heavy2d = false;              // 2-D kernels with the heavy closure interface: mixtures, axisymmetric dry air / table gas
   bool les = false;                  // dry air with a sub-grid scale model or a viscous sponge: the LES flavour of the kernels
@@ -102,6 +103,7 @@ inline OperatorPlan plan_operator(int mesh_dim, const tpsrhs_disc &disc, const t
   pl.order = disc.order;
   pl.nvel = axi ? 3 : pl.dim;
   pl.neq = pl.nvel + 2;
+  pl.sp_first = pl.sp_last = pl.nvel + 2;
   if (plasma) {
     const tpsrhs_perfect_mixture &mx = phys.mixture;
     if (!mx.is_electron_included) throw Unsupported("USER_DEFINED fluids without electrons are not built");
@@ -114,7 +116,8 @@ inline OperatorPlan plan_operator(int mesh_dim, const tpsrhs_disc &disc, const t
     if (phys.transport_model != TPSRHS_CONSTANT && phys.transport_model != TPSRHS_ARGON_MINIMAL &&
         phys.transport_model != TPSRHS_ARGON_MIXTURE)
       throw Unsupported("transport model outside the built scope (constant, argon_minimal, argon_mixture)");
-    pl.neq = pl.nvel + 2 + (mx.ambipolar ? mx.num_species - 2 : mx.num_species - 1) + (mx.two_temperature ? 1 : 0);
+    pl.sp_last = pl.sp_first + (mx.ambipolar ? mx.num_species - 2 : mx.num_species - 1);
+    pl.neq = pl.sp_last + (mx.two_temperature ? 1 : 0);
     pl.transport = (phys.transport_model == TPSRHS_CONSTANT)
                        ? PLAN_TRANSPORT_CONSTANT
                        : (phys.transport_model == TPSRHS_ARGON_MINIMAL ? PLAN_TRANSPORT_ARGON_MINIMAL : PLAN_TRANSPORT_ARGON_MIXTURE);

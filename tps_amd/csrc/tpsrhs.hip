@@ -350,8 +350,10 @@ void setup(tpsrhs_operator *op, const tpsrhs_mesh *mesh, const tpsrhs_disc *disc
   op->device = rt ? rt->device : 0;
   HIP_CHECK(hipSetDevice(op->device));
   op->stream = rt ? static_cast<hipStream_t>(rt->stream) : nullptr;
-  if (const char *env = std::getenv("TPSRHS_SWEEP_ALT")) op->sweep_alt = env[0] != '0';  // (A/B switch; default on)
-  if (const char *env = std::getenv("TPSRHS_FUSE_TRACES")) op->fuse_traces = env[0] != '0';  // (A/B switch; default on)
+  if (const char *env = std::getenv("TPSRHS_SWEEP_ALT")) op->loop.sweep_alt = env[0] != '0';  // (A/B switch; default on)
+  if (const char *env = std::getenv("TPSRHS_FUSE_TRACES")) op->loop.chain.set_fusing(env[0] != '0');  // (A/B switch; default on)
+  op->loop.sp_first = pl.sp_first;
+  op->loop.sp_last = pl.sp_last;
   op->halo = rt ? rt->halo : nullptr;
   op->halo_ctx = rt ? rt->halo_ctx : nullptr;
   op->reduce = rt ? rt->reduce : nullptr;
@@ -495,10 +497,11 @@ int tpsrhs_create(const tpsrhs_mesh *mesh, const tpsrhs_disc *disc, const tpsrhs
 }
 
 int tpsrhs_destroy(tpsrhs_handle h) {
-  if (h) stats_release(h);
-  if (h) transfer_release(h);
-  if (h) sampling_release(h);
-  if (h) integrals_release(h);
+  if (!h) return TPSRHS_OK;
+  stats_release(h);
+  transfer_release(h);
+  sampling_release(h);
+  integrals_release(h);
   delete h;
   return TPSRHS_OK;
 }
@@ -537,23 +540,42 @@ int tpsrhs_mult_host(tpsrhs_handle h, const double *x, double *y, double time, d
   });
 }
 
+// ---- the device time loop ------------------------------------------------------------------------------------------------
+// Its state is tpsrhs_operator::loop; the rules are in trace_chain.hpp.  The functions stay in this order, and rk_stages
+// after every other launch of this unit: the compiler numbers a unit's kernels by their first launch in the source, and
+// tools/device_asm_diff.py compares the local labels that carry that number.
 namespace {
+// The stage vectors in loop.d_rk (3 n doubles, with loop.d_nan allocated at the first step): k | y | z, or k | y with y on
+// an even offset, so that an odd n keeps the 16-byte accesses (y then ends at or before 2 n + 1 <= 3 n).
+struct StageScratch {
+  double *k, *y, *z;
+};
+StageScratch stage_scratch(tpsrhs_operator *h, int64_t n, bool even_offsets) {
+  tpsrhs_operator::TimeLoop &lp = h->loop;
+  if (!lp.d_rk) {
+    lp.d_rk = DevBuf<double>(3 * n);
+    lp.d_nan = DevBuf<unsigned long long>(1);
+    HIP_CHECK(hipMemsetAsync(lp.d_nan.get(), 0, sizeof(unsigned long long), h->stream));
+  }
+  double *k = lp.d_rk.get();
+  if (even_offsets) return {k, k + ((n + 1) & ~static_cast<int64_t>(1)), nullptr};
+  return {k, k + n, k + 2 * n};
+}
+// {dt, time, max speed} of the loop in device memory; the probe and monitor records copy the time from there
+double *loop_ctl(tpsrhs_operator *h) {
+  if (!h->loop.d_ctl) h->loop.d_ctl = DevBuf<double>(3);
+  return h->loop.d_ctl.get();
+}
+
 // the four stages of MFEM's RK4Solver::Step around Mult; dt by value or from device memory (dt_dev)
 void rk4_stages(tpsrhs_operator *h, double *x, double dt, const double *dt_dev) {
   const int64_t n = static_cast<int64_t>(h->neq) * h->ndofs;
-  if (!h->d_rk) {
-    h->d_rk = DevBuf<double>(3 * n);
-    h->d_nan = DevBuf<unsigned long long>(1);
-    HIP_CHECK(hipMemsetAsync(h->d_nan.get(), 0, sizeof(unsigned long long), h->stream));
-  }
-  double *k = h->d_rk.get(), *y = k + n, *z = y + n;
-  if (!h->ta_chain) h->ta_valid = false;  // a step starts with its own k_traces sweep: x may have been touched since the
-                                          // last call (tpsrhs_advance chains its steps: nothing touches x between them)
-  const bool mixture = h->phys.working_fluid == TPSRHS_USER_DEFINED;
-  const int sp_first = h->nvel + 2;
-  const int sp_last = mixture ? sp_first + (h->phys.mixture.ambipolar ? h->phys.mixture.num_species - 2
-                                                                       : h->phys.mixture.num_species - 1)
-                              : sp_first;
+  const StageScratch sc = stage_scratch(h, n, false);
+  double *k = sc.k, *y = sc.y, *z = sc.z;
+  TraceChain &chain = h->loop.chain;
+  chain.begin_step();
+  ScopeExit step([&](bool) { chain.end_step(); });
+  const int sp_first = h->loop.sp_first, sp_last = h->loop.sp_last;
   const int grid = static_cast<int>(std::min<int64_t>((n + 255) / 256, 8192));
   if (!h->forcing_active) {
     // The stage combinations in k_flux's epilogue (RkDev, kernels.hpp): k never goes to memory, the accumulator of
@@ -574,25 +596,21 @@ void rk4_stages(tpsrhs_operator *h, double *x, double dt, const double *dt_dev) 
       r.y3 = y3;
       r.y4 = y4;
       r.out = outs[stage - 1];
-      r.nan_count = h->d_nan.get();
-      h->rk = r;
-      try {
-        h->launch(h, ins[stage - 1], outs[stage - 1], false);
-      } catch (...) {
+      r.nan_count = h->loop.d_nan.get();
+      h->rk = r;  // in force for this launch only
+      ScopeExit launched([&](bool failed) {
         h->rk = RkDev{};
-        h->ta_valid = false;
-        throw;
-      }
-      h->rk = RkDev{};
+        if (failed) chain.abandon();
+      });
+      h->launch(h, ins[stage - 1], outs[stage - 1], false);
     }
-    if (!h->ta_chain) h->ta_valid = false;
     return;
   }
   const double *in = x;
   for (int stage = 1; stage <= 4; stage++) {
     h->launch(h, in, k, false);  // k_s = f(stage input); SetTime is a no-op for this operator
     hipLaunchKernelGGL(k_rk4_stage<256>, dim3(grid), dim3(256), 0, h->stream, stage, n, h->ndofs, sp_first, sp_last, dt,
-                       dt_dev, x, k, y, z, h->d_nan.get());
+                       dt_dev, x, k, y, z, h->loop.d_nan.get());
     HIP_CHECK(hipGetLastError());
     in = y;
   }
@@ -659,7 +677,7 @@ int step_with(tpsrhs_handle h, int integrator, const char *who, double *x, doubl
   return guarded([&] {
     HIP_CHECK(hipSetDevice(h->device));
     h->nr_dt = dt;  // the boundary conditions see M2ulPhyS::dt (src/BoundaryCondition.hpp:54)
-    if (h->d_nan.get()) HIP_CHECK(hipMemsetAsync(h->d_nan.get(), 0, sizeof(unsigned long long), h->stream));
+    if (h->loop.d_nan) HIP_CHECK(hipMemsetAsync(h->loop.d_nan.get(), 0, sizeof(unsigned long long), h->stream));
     step_stages(h, integrator, x, dt, nullptr);
     *time += dt;
     if (max_char_speed || nan_count) {
@@ -668,7 +686,7 @@ int step_with(tpsrhs_handle h, int integrator, const char *who, double *x, doubl
       double speed = 0.0;
       unsigned long long bad = 0;
       HIP_CHECK(hipMemcpyAsync(&speed, h->d_speed.get(), sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      HIP_CHECK(hipMemcpyAsync(&bad, h->d_nan.get(), sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+      HIP_CHECK(hipMemcpyAsync(&bad, h->loop.d_nan.get(), sizeof(bad), hipMemcpyDeviceToHost, h->stream));
       HIP_CHECK(hipStreamSynchronize(h->stream));
       if (max_char_speed) *max_char_speed = speed;
       if (nan_count) *nan_count = static_cast<int64_t>(bad);
@@ -688,19 +706,19 @@ int advance_with(tpsrhs_handle h, int integrator, const char *who, double *x, do
     HIP_CHECK(hipSetDevice(h->device));
     if (!constant_dt && h->topo.num_shared > 0 && !h->reduce)
       throw std::runtime_error("halo: a variable time step on a partitioned mesh needs runtime.reduce");
-    if (!h->d_ctl) h->d_ctl = DevBuf<double>(3);
+    double *const d_ctl = loop_ctl(h);
     const double ctl0[3] = {*dt, *time, 0.0};
-    HIP_CHECK(hipMemcpyAsync(h->d_ctl.get(), ctl0, sizeof(ctl0), hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipMemcpyAsync(d_ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice, h->stream));
     HIP_CHECK(hipStreamSynchronize(h->stream));  // ctl0 lives on this stack frame
-    if (h->d_nan.get()) HIP_CHECK(hipMemsetAsync(h->d_nan.get(), 0, sizeof(unsigned long long), h->stream));
-    h->nr_dt_dev = h->d_ctl.get();
+    if (h->loop.d_nan) HIP_CHECK(hipMemsetAsync(h->loop.d_nan.get(), 0, sizeof(unsigned long long), h->stream));
+    const double coef = cfl * hmin / static_cast<double>(h->dim);
     auto one_step = [&] {
-      step_stages(h, integrator, x, 0.0, h->d_ctl.get());
-      hipLaunchKernelGGL(k_step_end<1024>, dim3(1), dim3(1024), 0, h->stream, h->flux_grid, h->d_block_speed.get(), h->d_ctl.get(),
-                         constant_dt ? 1 : 0, cfl * hmin / static_cast<double>(h->dim));
+      step_stages(h, integrator, x, 0.0, d_ctl);
+      hipLaunchKernelGGL(k_step_end<1024>, dim3(1), dim3(1024), 0, h->stream, h->flux_grid, h->d_block_speed.get(), d_ctl,
+                         constant_dt ? 1 : 0, coef);
       HIP_CHECK(hipGetLastError());
       if (!constant_dt && h->reduce && h->topo.num_shared > 0) {  // MPI_Allreduce(MIN) of src/M2ulPhyS.cpp:2015
-        if (h->reduce(h->reduce_ctx, h->d_ctl.get(), 1, TPSRHS_REDUCE_MIN, h->stream) != 0)
+        if (h->reduce(h->reduce_ctx, d_ctl, 1, TPSRHS_REDUCE_MIN, h->stream) != 0)
           throw std::runtime_error("halo: reduce callback failed");
       }
     };
@@ -711,14 +729,15 @@ int advance_with(tpsrhs_handle h, int integrator, const char *who, double *x, do
     const char *genv = std::getenv("TPSRHS_GRAPH");
     const bool use_graph = h->stream != nullptr && h->topo.num_shared == 0 && !h->timing && num_steps >= 3 &&
                            !(genv && genv[0] == '0');
-    // A replayed graph must leave the boundary-state buffers as it found them, and they swap once per Mult: with
-    // non-reflecting faces a scheme with an odd number of Mults per step (Euler 1, RK3 3) is captured two steps at a time.
-    const int mults_per_step = integrator == TPSRHS_RK4 ? 4 : integrator;
-    const int steps_per_graph = (h->n_nr_faces > 0 && (mults_per_step & 1)) ? 2 : 1;
-    h->ta_valid = false;
-    // (with forcing terms the stage kernel runs and nothing is fused; the other integrators never enter the trace chain)
-    h->ta_chain = integrator == TPSRHS_RK4 && !h->forcing_active;
-    try {
+    const int per_graph = steps_per_graph(integrator, h->n_nr_faces > 0);
+    {
+      // the session: the boundary conditions read dt from device memory, the steps are chained; put back however it ends
+      h->nr_dt_dev = d_ctl;
+      h->loop.chain.begin_advance(integrator == TPSRHS_RK4 && !h->forcing_active);
+      ScopeExit session([&](bool) {
+        h->nr_dt_dev = nullptr;
+        h->loop.chain.end_advance();
+      });
       // Running statistics and probe records: the host issues every step anyway and knows the iteration number, so it
       // enqueues the sample or the record between two steps -- never inside the captured graph, whose key knows about neither.
       int step = 0;
@@ -726,42 +745,25 @@ int advance_with(tpsrhs_handle h, int integrator, const char *who, double *x, do
         one_step();  // first step outside the graph: allocations, initial boundary state, its own k_traces sweep
         after_step(h, x);
         step = 1;
-        tpsrhs_operator::StepKey key;
+        StepKey key;
         key.x = x;
         key.constant_dt = constant_dt ? 1 : 0;
         key.bstate_cur = h->bstate_cur;
-        key.epoch = h->config_epoch;
+        key.epoch = h->loop.config_epoch;
         key.integrator = integrator;
-        key.coef = cfl * hmin / static_cast<double>(h->dim);
-        if (!h->step_graph || !(h->step_key == key)) {
-          if (h->step_graph) {
-            HIP_CHECK(hipGraphExecDestroy(h->step_graph));
-            h->step_graph = nullptr;
-          }
-          hipGraph_t g = nullptr;
-          HIP_CHECK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-          try {
-            for (int i = 0; i < steps_per_graph; i++) one_step();
-          } catch (...) {
-            (void)hipStreamEndCapture(h->stream, &g);
-            if (g) (void)hipGraphDestroy(g);
-            throw;
-          }
-          HIP_CHECK(hipStreamEndCapture(h->stream, &g));
-          const hipError_t ie = hipGraphInstantiate(&h->step_graph, g, nullptr, nullptr, 0);
-          (void)hipGraphDestroy(g);
-          HIP_CHECK(ie);
-          h->step_key = key;
-        }
-        for (; step + steps_per_graph <= num_steps; step += steps_per_graph) {
+        key.coef = coef;
+        h->loop.graph.ensure(key, h->stream, [&] {
+          for (int i = 0; i < per_graph; i++) one_step();
+        });
+        for (; step + per_graph <= num_steps; step += per_graph) {
           // a sample or a record between the two steps of one graph: the pair runs as two plain steps (bit-equal to the
           // replay, as the odd remainder below is), which leave the boundary-state buffers as the graph does
-          const bool split = steps_per_graph == 2 && work_due_after_next(h);
-          for (int i = 0; i < steps_per_graph; i++) {
+          const bool split = per_graph == 2 && work_due_after_next(h);
+          for (int i = 0; i < per_graph; i++) {
             if (split)
               one_step();
             else if (i == 0)
-              HIP_CHECK(hipGraphLaunch(h->step_graph, h->stream));
+              h->loop.graph.launch(h->stream);
             after_step(h, x);
           }
         }
@@ -770,17 +772,11 @@ int advance_with(tpsrhs_handle h, int integrator, const char *who, double *x, do
         one_step();
         after_step(h, x);
       }
-    } catch (...) {
-      h->nr_dt_dev = nullptr;
-      h->ta_chain = h->ta_valid = false;
-      throw;
     }
-    h->nr_dt_dev = nullptr;
-    h->ta_chain = h->ta_valid = false;  // the caller owns x again
     double ctl[3] = {0, 0, 0};
     unsigned long long bad = 0;
-    HIP_CHECK(hipMemcpyAsync(ctl, h->d_ctl.get(), sizeof(ctl), hipMemcpyDeviceToHost, h->stream));
-    if (h->d_nan.get()) HIP_CHECK(hipMemcpyAsync(&bad, h->d_nan.get(), sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipMemcpyAsync(ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, h->stream));
+    if (h->loop.d_nan) HIP_CHECK(hipMemcpyAsync(&bad, h->loop.d_nan.get(), sizeof(bad), hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(hipStreamSynchronize(h->stream));
     *dt = ctl[0];
     *time = ctl[1];
@@ -934,16 +930,18 @@ int tpsrhs_set_forcing(tpsrhs_handle h, const tpsrhs_forcing *in) {
     const ForcingDev prev = h->forcing;
     const bool prev_active = h->forcing_active;
     h->forcing = f;
-    try {
+    {
+      ScopeExit rollback([&](bool failed) {
+        if (failed) {
+          h->forcing = prev;
+          h->forcing_active = prev_active;
+        }
+      });
       upload_forcing(h);  // synchronises the stream before it overwrites the device block
       HIP_CHECK(hipStreamSynchronize(h->stream));
-    } catch (...) {
-      h->forcing = prev;
-      h->forcing_active = prev_active;
-      throw;
     }
     h->d_mixed_out.swap(mixed_out);
-    h->config_epoch++;
+    h->loop.config_epoch++;
   });
 }
 
@@ -965,7 +963,7 @@ int tpsrhs_set_mixing_length(tpsrhs_handle h, const double *distance, const tpsr
     } else {
       h->mixlen.distance = nullptr;
     }
-    h->config_epoch++;  // a captured time-loop graph holds the old pointer
+    h->loop.config_epoch++;  // a captured time-loop graph holds the old pointer
   });
 }
 
@@ -975,7 +973,7 @@ int tpsrhs_set_joule_heating(tpsrhs_handle h, const double *joule_heating) {
     // JouleHeating::updateTerms asserts nvel == 3 (src/forcing_terms.cpp:444)
     if (joule_heating && h->nvel != 3) throw Unsupported("JouleHeating needs three velocity components (3-D or axisymmetric)");
     h->forcing.joule = joule_heating;
-    h->config_epoch++;
+    h->loop.config_epoch++;
     upload_forcing(h);
   });
 }
@@ -1171,10 +1169,9 @@ const char *tpsrhs_version(void) { return "tpsrhs 0.1.0 (gfx950)"; }
 
 namespace {
 // Forward Euler, RK2(a = 1) and RK3-SSP (time_integrators.hpp): the plain Mult (h->rk stays RkDev{}: k_flux writes the
-// residual, nothing enters the trace chain) and one k_rk_stage pass per stage.  k | y in the first two thirds of d_rk, y on
-// an even offset so that an odd length keeps the 16-byte accesses.  (Fusing these combinations into k_flux's epilogue, as
-// RK4 has, is left out on purpose: DESIGN.md section 9.)  Defined after every other launch of this unit, so that the
-// compiler numbers the kernels that were here before as it did before (tools/device_asm_diff.py compares their labels too).
+// residual, nothing enters the trace chain) and one k_rk_stage pass per stage.  (Fusing these combinations into k_flux's
+// epilogue, as RK4 has, is left out on purpose: DESIGN.md section 9.)  Here, after every other launch of this unit: see
+// the head of the time loop's section.
 template <int OP>
 void rk_stage(tpsrhs_operator *h, int64_t n, int64_t clamp_lo, int64_t clamp_hi, double dt, const double *dt_dev, double *x,
               const double *k, double *y) {
@@ -1183,28 +1180,21 @@ void rk_stage(tpsrhs_operator *h, int64_t n, int64_t clamp_lo, int64_t clamp_hi,
   const int grid = static_cast<int>(std::min<int64_t>((items + 255) / 256, 8192));  // the grid cap of k_rk4_stage
   if (vec)
     hipLaunchKernelGGL((k_rk_stage<OP, true, 256>), dim3(grid), dim3(256), 0, h->stream, n, clamp_lo, clamp_hi, dt, dt_dev, x, k, y,
-                       h->d_nan.get());
+                       h->loop.d_nan.get());
   else
     hipLaunchKernelGGL((k_rk_stage<OP, false, 256>), dim3(grid), dim3(256), 0, h->stream, n, clamp_lo, clamp_hi, dt, dt_dev, x, k, y,
-                       h->d_nan.get());
+                       h->loop.d_nan.get());
   HIP_CHECK(hipGetLastError());
 }
 
 void rk_stages(tpsrhs_operator *h, int integrator, double *x, double dt, const double *dt_dev) {
   const int64_t n = static_cast<int64_t>(h->neq) * h->ndofs;
-  if (!h->d_rk) {
-    h->d_rk = DevBuf<double>(3 * n);
-    h->d_nan = DevBuf<unsigned long long>(1);
-    HIP_CHECK(hipMemsetAsync(h->d_nan.get(), 0, sizeof(unsigned long long), h->stream));
-  }
-  double *k = h->d_rk.get(), *y = k + ((n + 1) & ~static_cast<int64_t>(1));  // y ends at or before 2 n + 1 <= 3 n
-  h->ta_valid = false;  // every Mult of these schemes runs its own k_traces sweep
-  const bool mixture = h->phys.working_fluid == TPSRHS_USER_DEFINED;
-  const int sp_first = h->nvel + 2;
-  const int sp_last = mixture ? sp_first + (h->phys.mixture.ambipolar ? h->phys.mixture.num_species - 2
-                                                                       : h->phys.mixture.num_species - 1)
-                              : sp_first;
-  const int64_t lo = sp_first * h->ndofs, hi = sp_last * h->ndofs;  // Check_Undershoot's rows, contiguous in [neq][ndofs]
+  const StageScratch sc = stage_scratch(h, n, true);
+  double *k = sc.k, *y = sc.y;
+  h->loop.chain.begin_step();  // every Mult of these schemes runs its own k_traces sweep
+  ScopeExit step([h](bool) { h->loop.chain.end_step(); });
+  // Check_Undershoot's rows, contiguous in [neq][ndofs]
+  const int64_t lo = h->loop.sp_first * h->ndofs, hi = h->loop.sp_last * h->ndofs;
   h->launch(h, x, k, false);  // k = f(x); SetTime is a no-op for this operator
   if (integrator == TPSRHS_FORWARD_EULER) {
     rk_stage<RK_EULER>(h, n, lo, hi, dt, dt_dev, x, k, y);
@@ -1460,7 +1450,7 @@ void probe_record(tpsrhs_operator *h, const double *x) {
   if (r < 0) return;
   const int64_t per = static_cast<int64_t>(h->neq) * log.sampler->npts;
   sample_field(h, log.sampler, h->neq, x, log.d_values.get() + r * per);
-  HIP_CHECK(hipMemcpyAsync(log.d_times.get() + r, h->d_ctl.get() + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  HIP_CHECK(hipMemcpyAsync(log.d_times.get() + r, h->loop.d_ctl.get() + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
 }
 
 // the position of s among the samplers of ss, or their end
@@ -1772,7 +1762,7 @@ int tpsrhs_probe_configure(tpsrhs_handle h, tpsrhs_sampler_handle s, int64_t int
     log.index.capacity = capacity;
     log.d_values = DevBuf<double>(capacity * h->neq * s->npts);
     log.d_times = DevBuf<double>(capacity);
-    if (!h->d_ctl) h->d_ctl = DevBuf<double>(3);  // the loop's {dt, time, max speed}: a record copies the time from there
+    loop_ctl(h);  // a record copies the time from there
     // complete: a call that throws above leaves the probes off.  (h->sampling exists: s is one of its samplers)
     h->sampling->probe = std::move(log);
   });
@@ -1963,8 +1953,8 @@ void monitor_record(tpsrhs_operator *h, const double *x) {
   integrate_field(h, h->neq, x, nullptr, axisym, log.d_totals.get() + r * h->neq, nullptr);
   nodal_stats_field(h, h->neq, x, log.d_mins.get() + r * h->neq, log.d_maxs.get() + r * h->neq, nullptr);
   // {dt of the next step, time}: the loop's control block, which the variable-dt loop never has on the host
-  HIP_CHECK(hipMemcpyAsync(log.d_dts.get() + r, h->d_ctl.get(), sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  HIP_CHECK(hipMemcpyAsync(log.d_times.get() + r, h->d_ctl.get() + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  HIP_CHECK(hipMemcpyAsync(log.d_dts.get() + r, h->loop.d_ctl.get(), sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  HIP_CHECK(hipMemcpyAsync(log.d_times.get() + r, h->loop.d_ctl.get() + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
 }
 }  // namespace
 
@@ -2014,7 +2004,7 @@ int tpsrhs_monitor_configure(tpsrhs_handle h, int64_t interval, int64_t capacity
     log.d_totals = DevBuf<double>(capacity * h->neq);
     log.d_mins = DevBuf<double>(capacity * h->neq);
     log.d_maxs = DevBuf<double>(capacity * h->neq);
-    if (!h->d_ctl) h->d_ctl = DevBuf<double>(3);  // the loop's {dt, time, max speed}: a record copies from there
+    loop_ctl(h);  // a record copies dt and the time from there
     is->monitor = std::move(log);  // complete: a call that throws above leaves the monitor off
   });
 }
