@@ -391,6 +391,13 @@ int tpsrhs_table_eval(const tpsrhs_table *table, int64_t n, const double *x, dou
  * 3 log of a positive finite argument, 4 reciprocal, 5 sqrt, 6 reciprocal sqrt. */
 int tpsrhs_math_eval(int function, int64_t n, const double *x, double *y);
 
+/* Diagnostic: the eight Coulomb collision fits of the third-order electron conductivity (att11, rep22, rep23, rep24,
+ * att12 .. att15 of src/collision_integrals.cpp:53-115) without their factor 1 / Tp^2, c0 log(1 + c1 e^(c2 x))^c3, at
+ * n arguments x = ln Tp; out[f * n + i] (x, out: device pointers, synchronous).  Route 0: the formulas through the
+ * device's exp / log; 1: the polynomial table of the 3-D p = 3 sweeps (tps_amd/csrc/coulomb_table.hpp) with wave-uniform
+ * coefficient loads; 2: the same table read lane by lane.  Arguments off the table (and NaN) take route 0 in every route. */
+int tpsrhs_coulomb_eval(int route, int64_t n, const double *x, double *out);
+
 int64_t tpsrhs_height(tpsrhs_handle h);
 int64_t tpsrhs_num_dofs(tpsrhs_handle h);
 int tpsrhs_num_equation(tpsrhs_handle h);

@@ -207,6 +207,18 @@ struct Cfg {
   static constexpr int Q2_ROUNDS = (TQ2 + BLOCK - 1) / BLOCK;
 };
 
+// Which sweeps take the Coulomb fits of their closure from the polynomial table (PlasmaPhys::transport_coeffs<CTAB>): the
+// argon-minimal ternary physics at 3-D, p = 3, collocated -- k_gradient's face points and k_flux's nodes, in either form of
+// the lean face kernel (the key does not look at TPSRHS_LEAN_GENERAL: the two forms stay bit-identical).
+template <class PH, class = void>
+struct lean_one_hex : std::false_type {};
+template <class PH>
+struct lean_one_hex<PH, std::enable_if_t<PH::LEAN_ONE_HEX>> : std::true_type {};
+template <class C, class PH>
+constexpr bool coulomb_tab() {
+  return lean_one_hex<PH>::value && C::DIM == 3 && C::P == 3 && C::NC == 0;
+}
+
 // LDS copy of the tables that are indexed per lane
 template <class C>
 struct Tab {
@@ -1684,7 +1696,10 @@ __device__ inline void visc_phase_lean3d(const MeshDev &m, const int2 *sFI, type
         double Us[NEQ];
         typename PH::WallFlux w;
         PH::visc_pass_state(pq, nb, pass, u, n, Us, w);
-        PH::visc_point_lean(pq, Us, w, cf);
+        if constexpr (coulomb_tab<C, PH>())
+          PH::template visc_point_lean<true>(pq, Us, w, cf);
+        else
+          PH::visc_point_lean(pq, Us, w, cf);
       }
       STAMP(6);
       double gv[DIM * DIM], gn[NEQ];
@@ -1943,7 +1958,10 @@ __device__ inline void visc_phase_lean1(const MeshDev &m, const int2 *sFI, typen
         double Us[NEQ];
         typename PH::WallFlux w;
         PH::visc_pass_state(pq, nb, pass, u, n, Us, w);
-        PH::visc_point_lean(pq, Us, w, cf);
+        if constexpr (coulomb_tab<C, PH>())
+          PH::template visc_point_lean<true>(pq, Us, w, cf);
+        else
+          PH::visc_point_lean(pq, Us, w, cf);
       }
       STAMP(6);
       double gv[DIM * DIM], gn[NEQ];
@@ -2939,7 +2957,10 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && (PH::HEAVY || PH::MINW_FLUX > 2
       const typename PH::State st = PH::make_state(prm, uc);
       speed = PH::max_char_speed(prm, uc, st);
       typename PH::FluxCoef fc;
-      if constexpr (PH::TWO_STEP) PH::flux_coeffs(prm, uc, st, fc);
+      if constexpr (coulomb_tab<C, PH>())
+        PH::template flux_coeffs<true>(prm, uc, st, fc);
+      else if constexpr (PH::TWO_STEP)
+        PH::flux_coeffs(prm, uc, st, fc);
       if (PH::HAS_SOURCE) {
         double up[NEQ];
         PH::prim(prm, u, up);

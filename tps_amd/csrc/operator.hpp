@@ -90,6 +90,7 @@ struct tpsrhs_operator {
   DevBuf<void> d_chem;                // ChemDev block (plasma)
   DevBuf<void> d_params;              // device image of `params` for the physics that read it through a pointer (plasma)
   std::vector<DevBuf<void>> d_extra;  // what the parameter block points to: table coefficients, search aids, element sizes
+  DevBuf<double> d_coulomb;           // coulomb_table.hpp: the Coulomb fits of the 3-D p = 3 argon-minimal sweeps (PlasmaParams::ctab)
   std::vector<DevBuf<void>> d_mixed_out;  // plane-node lists / sum buffers of the current forcing's mixed-out sponge zones
   DevBuf<double> d_verts;
   DevBuf<int2> d_face_info;

@@ -41,6 +41,9 @@ struct OperatorPlan {
   double sponge_n[3] = {0, 0, 0}, sponge_p[3] = {0, 0, 0}, sponge_width = 1.0, sponge_ratio = 1.0;
   double sgs_const = 0.0;  // les: sgs.model_const or the reference's default for the model
   int transport = 0;       // plasma: PLAN_TRANSPORT_*
+  // plasma: the sweeps of this operator read the Coulomb fits from the polynomial table (kernels.hpp::coulomb_tab: 3-D,
+  // p = 3, collocated, single-temperature argon-minimal ternary mixture), which the build then uploads
+  bool coulomb_table = false;
   std::string unit;        // plasma: the kernel family, plasma_<geo>_n<species>[a][_hi]
 };
 
@@ -127,6 +130,8 @@ inline OperatorPlan plan_operator(int mesh_dim, const tpsrhs_disc &disc, const t
     const char *geo = (pl.dim == 3) ? "3d" : (axi ? "axi" : "2d");
     pl.unit = std::string("plasma_") + geo + "_n" + std::to_string(mx.num_species) + (mx.ambipolar ? "a" : "") +
               ((pl.order >= 4 && !pl.nc) ? "_hi" : "");
+    pl.coulomb_table = pl.dim == 3 && pl.order == 3 && !pl.nc && mx.num_species == 3 && !mx.two_temperature &&
+                       phys.transport_model == TPSRHS_ARGON_MINIMAL;
   }
   // Fluxes: sub-grid scale model and viscous sponge (src/fluxes.cpp:223-246).  The 2-D kernels with the heavy interface
   // take the sponge plane in MeshDev and scale their coefficients (:232-246); dry air, planar and 3-D, takes both in the

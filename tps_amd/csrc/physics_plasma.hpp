@@ -19,6 +19,12 @@
 #include <hip/hip_runtime.h>
 
 #include "physics_dryair.hpp"
+// (the host build of the point physics, tests/host_physics, copies this header without its neighbours: it evaluates the
+// exact formulas only and never instantiates a closure with CTAB)
+#if __has_include("coulomb_table.hpp")
+#include "coulomb_table.hpp"
+#define TPSRHS_HAVE_COULOMB_TABLE 1
+#endif
 
 namespace tpsrhs {
 
@@ -83,6 +89,9 @@ struct PlasmaParams {
   const ChemDev *chem;
   int eq_system, use_bc_in_grad, num_bcs, axisymmetric;
   BcDev bc[PLASMA_MAXBC];
+  // coulomb_table.hpp: the eight Coulomb fits of the third-order k_e as piecewise polynomials in ln Tp, device memory of the
+  // operator; NULL: the formulas.  Read only by the closures compiled with CTAB (3-D, p = 3, argon-minimal ternary).
+  const double *ctab;
 };
 
 __device__ inline double ipow(double x, int k) {  // pow(x, small non-negative integer), pow(0,0) = 1
@@ -179,6 +188,86 @@ __device__ inline double att15(const Arg &a) { return cfit(0.0232, 13.7888, 0.91
 __device__ inline double rep22(const Arg &a) { return cfit(0.4128, 1.2436, 1.1830, 1.0123, a); }
 __device__ inline double rep23(const Arg &a) { return cfit(0.2203, 1.8832, 1.2059, 0.9851, a); }
 __device__ inline double rep24(const Arg &a) { return cfit(0.1323, 2.7248, 1.2129, 0.9847, a); }
+// The eight fits of the third-order electron conductivity, four at a time for cfit_n -- and, in this order (kFitA, then
+// kFitB), the fits 0 .. 7 of the polynomial table (coulomb_table.hpp), which is filled from these literals.
+constexpr double kFitA[4][4] = {{0.2150, 5.2194, 1.0472, 1.2435},   // att11
+                                {0.4128, 1.2436, 1.1830, 1.0123},   // rep22
+                                {0.2203, 1.8832, 1.2059, 0.9851},   // rep23
+                                {0.1323, 2.7248, 1.2129, 0.9847}};  // rep24
+constexpr double kFitB[4][4] = {{0.0991, 7.4684, 1.0155, 1.1536},    // att12
+                                {0.0616, 7.8271, 0.9452, 1.1105},    // att13
+                                {0.0308, 13.9567, 0.9511, 1.1803},   // att14
+                                {0.0232, 13.7888, 0.9148, 1.1532}};  // att15
+#ifdef TPSRHS_HAVE_COULOMB_TABLE
+// How many distinct intervals of a wave are evaluated with wave-uniform (scalar) coefficient loads before the lanes that
+// are left load theirs lane by lane.  0: per-lane loads only -- the fastest of 0, 1, 2, 4 on the metric's workload (DESIGN.md
+// section 5): a uniform round is a readfirstlane, ten scalar loads that the free SGPRs admit a few at a time, and a wait for
+// each batch; a hex spans two or three intervals, and the rounds cost more than the transcendental chains they replace.
+#ifndef TPSRHS_COULOMB_UNIFORM
+#define TPSRHS_COULOMB_UNIFORM 0
+#endif
+inline void coulomb_table_fill(double *table) {  // host: table[coulomb::SIZE]
+  double c[coulomb::NFIT][4];
+  for (int f = 0; f < 4; f++)
+    for (int k = 0; k < 4; k++) {
+      c[f][k] = kFitA[f][k];
+      c[4 + f][k] = kFitB[f][k];
+    }
+  coulomb::fill(c, table);
+}
+// g[f] = c0 [log(1 + c1 e^(c2 x))]^c3 of the table's first NF fits in the lanes with `todo` set, whose x is on the table
+// (the other lanes keep their g).  NUNI times, the lanes that share the interval of the first unfinished lane evaluate it
+// with coefficients read through the CONSTANT address space -- scalar loads, the Horner steps take them as SGPR operands;
+// whoever is left reads the same coefficients lane by lane and runs the same steps: a lane's bits do not depend on its
+// route, that is on what the other lanes of its wave hold.
+template <int NF, int NUNI>
+__device__ inline void ctab_eval(const double *tab, double x, bool todo, double (&g)[NF]) {
+  const double xs = todo ? x : coulomb::X0;
+  const int idx = coulomb::interval(xs);
+  const double t = coulomb::local(xs, idx);
+  // (the table's address is wave-uniform; inside divergent control flow it may sit in VGPRs: PlasmaPhys::relaunder)
+  const unsigned long long a = reinterpret_cast<unsigned long long>(tab);
+  const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(a));
+  const unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(a >> 32));
+  const double __attribute__((address_space(4))) *ctab =
+      reinterpret_cast<const double __attribute__((address_space(4))) *>((static_cast<unsigned long long>(hi) << 32) | lo);
+#pragma unroll
+  for (int r = 0; r < NUNI; r++) {
+    if (todo) {
+      const int u = __builtin_amdgcn_readfirstlane(idx);
+      if (idx == u) {
+        coulomb::horner<NF>(ctab + u * coulomb::STRIDE, t, g);
+        todo = false;
+      }
+    }
+  }
+  if (todo) coulomb::horner<NF>(tab + idx * coulomb::STRIDE, t, g);
+}
+// the fits of kFitA and kFitB (NF = 8), or att11 and rep22 alone (NF = 2), at one argument: from the table where there
+// is one and ln Tp is on it, else -- a NaN, an extreme state -- through cfit_n exactly as without a table
+template <int NF>
+__device__ inline void cfit_tab(const double *tab, const Arg &a, double (&out)[NF]) {
+  static_assert(NF == 2 || NF == 8, "att11 and rep22, or all eight");
+  const bool on = tab != nullptr && coulomb::in_range(a.ln);
+  if (on) {
+    ctab_eval<NF, TPSRHS_COULOMB_UNIFORM>(tab, a.ln, true, out);
+#pragma unroll
+    for (int f = 0; f < NF; f++) out[f] *= a.inv2;
+  } else if constexpr (NF == 8) {
+    double A[4], B[4];
+    cfit_n<4>(kFitA, a, A);
+    cfit_n<4>(kFitB, a, B);
+#pragma unroll
+    for (int f = 0; f < 4; f++) {
+      out[f] = A[f];
+      out[4 + f] = B[f];
+    }
+  } else {
+    out[0] = att11(a);
+    out[1] = rep22(a);
+  }
+}
+#endif
 // Coulomb fits by (attractive 0 / repulsive 1, l, r): c0, c1, c2, c3 (src/collision_integrals.cpp:53-115);
 // rows the reference does not have are zero
 __constant__ static double c_coulomb[2][2][5][4] = {
@@ -617,8 +706,15 @@ struct PlasmaPhys {
   //   1 / D_ij = n Q_ij sqrt(mu_ij) / (d_fc sqrt(T)) directly (CurtissHirschfelder only ever divides by D_ij);
   //   one reciprocal each of T_e, T_h, n, X_sp + eps, shared by everything that divides by them.
   // Results differ from the reference's order by rounding (a few ulp).
+  // CTAB: the Coulomb fits of the argon-minimal ternary closure from the polynomial table p.ctab (coll::cfit_tab) -- the
+  // sweeps of the 3-D p = 3 collocated operator only (kernels.hpp::coulomb_tab); every other caller keeps the formulas.
+  template <bool CTAB = false>
   __device__ static inline void transport_coeffs(PRef p, const double *U, double Th, double Te, bool diffusion,
                                                  TCoef &t) {
+#ifndef TPSRHS_HAVE_COULOMB_TABLE
+    static_assert(!CTAB, "coulomb_table.hpp is not part of this build");
+#endif
+    static_assert(!CTAB || (!TWOT && TRANSPORT == TRANSPORT_ARGON_MINIMAL), "the table serves the single-temperature argon-minimal closure");
     const Species q = species(p, U);
 #pragma unroll
     for (int sp = 0; sp < NSP; sp++) {
@@ -722,17 +818,23 @@ struct PlasmaPhys {
       if (p.third_order) {
         // the eight Coulomb fits of the electron temperature and the five e-Ar polynomials, four / five at a time in
         // lock step (cfit_n, eAr1r_n: the same operations per fit, interleaved -- independent chains for the VALU)
-        constexpr double cA[4][4] = {{0.2150, 5.2194, 1.0472, 1.2435},   // att11
-                                     {0.4128, 1.2436, 1.1830, 1.0123},   // rep22
-                                     {0.2203, 1.8832, 1.2059, 0.9851},   // rep23
-                                     {0.1323, 2.7248, 1.2129, 0.9847}};  // rep24
-        constexpr double cB[4][4] = {{0.0991, 7.4684, 1.0155, 1.1536},    // att12
-                                     {0.0616, 7.8271, 0.9452, 1.1105},    // att13
-                                     {0.0308, 13.9567, 0.9511, 1.1803},   // att14
-                                     {0.0232, 13.7888, 0.9148, 1.1532}};  // att15
+        // (coll::kFitA: att11, rep22, rep23, rep24; coll::kFitB: att12 .. att15)
         double A[4], B[4], QN[5];
-        coll::cfit_n<4>(cA, d.e, A);
-        coll::cfit_n<4>(cB, d.e, B);
+#ifdef TPSRHS_HAVE_COULOMB_TABLE
+        if constexpr (CTAB) {
+          double g[8];
+          coll::cfit_tab<8>(p.ctab, d.e, g);
+#pragma unroll
+          for (int f = 0; f < 4; f++) {
+            A[f] = g[f];
+            B[f] = g[4 + f];
+          }
+        } else
+#endif
+        {
+          coll::cfit_n<4>(coll::kFitA, d.e, A);
+          coll::cfit_n<4>(coll::kFitB, d.e, B);
+        }
         coll::eAr1r_n<5>(lnTe, QN);
         Qatt = A[0] * d.circle;
         QeAr = QN[0];
@@ -742,8 +844,18 @@ struct PlasmaPhys {
         t.ke = third_order_ke(q.X, Q2, QI, QN, sTe, p.ke_fac3);
       } else {
         QeAr = coll::eAr1r(1, lnTe);
-        Qatt = coll::att11(d.e) * d.circle;
-        rep22h = coll::rep22(d.h) * d.circle;
+#ifdef TPSRHS_HAVE_COULOMB_TABLE
+        if constexpr (CTAB) {  // (single-temperature: d.h is d.e) the rows att11 and rep22 of the table alone
+          double g[2];
+          coll::cfit_tab<2>(p.ctab, d.e, g);
+          Qatt = g[0] * d.circle;
+          rep22h = g[1] * d.circle;
+        } else
+#endif
+        {
+          Qatt = coll::att11(d.e) * d.circle;
+          rep22h = coll::rep22(d.h) * d.circle;
+        }
         t.ke = p.ke_fac * sTe * q.X[I_E] * fast_rcp(TWOT ? coll::rep22(d.e) * d.circle : rep22h);
       }
       const double sv_ion = p.vf_sq_mwp[I_ION] * sTh * fast_rcp(rep22h);
@@ -999,9 +1111,10 @@ struct PlasmaPhys {
   }
   // closure of the nodal flux: everything of ComputeFluxTransportProperties that depends on the state alone
   typedef TCoef FluxCoef;
+  template <bool CTAB = false>
   __device__ static inline void flux_coeffs(PRef p, const double *U, const State &s, FluxCoef &c) {
     if (p.eq_system == TPSRHS_EULER) return;
-    transport_coeffs(p, U, s.Th, s.Te, true, c);
+    transport_coeffs<CTAB>(p, U, s.Th, s.Te, true, c);
   }
   __device__ static inline void total_flux(PRef p, const double *U, const State &s, const FluxCoef &c,
                                            const double *g, double radius, double *F, const EddyCtx &ec = eddy_off()) {
@@ -1425,10 +1538,11 @@ struct PlasmaPhys {
     double hf0, ef0, sf0[NACTIVE];                 // prescribed (wall) parts of the heavy / electron heat flux and species rows
     double hfc[NIN], efc[NIN], sfc[NACTIVE][NIN];  // the same three as linear maps of the inputs
   };
+  template <bool CTAB = false>
   __device__ static inline void visc_point_lean(PRef p, const double *U, const WallFlux &w, ViscLean &L) {
     const State s = make_state(p, U);
     TCoef t;
-    transport_coeffs(p, U, s.Th, s.Te, !w.species, t);
+    transport_coeffs<CTAB>(p, U, s.Th, s.Te, !w.species, t);
     double h[NSP];
     enthalpies(p, s, h);
     L.mu = t.visc;

@@ -105,6 +105,16 @@ TableDev upload_table(tpsrhs_operator *op, const tpsrhs_table &t) {
   return td;
 }
 
+// the polynomial table of the Coulomb fits (coulomb_table.hpp), filled once per process from the literals of the closure
+const std::vector<double> &coulomb_table_host() {
+  static const std::vector<double> table = [] {
+    std::vector<double> t(coulomb::SIZE);
+    coll::coulomb_table_fill(t.data());
+    return t;
+  }();
+  return table;
+}
+
 // the parameter block of the plasma kernels (plasma_params_host.hpp) into the operator, the chemistry block to the device
 template <int NSP>
 void fill_plasma_params(tpsrhs_operator *op, const tpsrhs_disc *disc, const tpsrhs_physics *phys, int num_bcs,
@@ -126,7 +136,16 @@ void fill_plasma_params(tpsrhs_operator *op, const tpsrhs_disc *disc, const tpsr
 void fill_mixture_params(tpsrhs_operator *op, const OperatorPlan &pl, const tpsrhs_disc *disc, const tpsrhs_physics *phys,
                          int num_bcs, const tpsrhs_bc *bcs) {
   switch (phys->mixture.num_species) {
-    case 3: fill_plasma_params<3>(op, disc, phys, num_bcs, bcs); break;
+    case 3:
+      fill_plasma_params<3>(op, disc, phys, num_bcs, bcs);
+      if (pl.coulomb_table) {  // TPSRHS_COULOMB_TABLE=0: the formulas (A/B switch within one library)
+        const char *env = std::getenv("TPSRHS_COULOMB_TABLE");
+        if (!env || env[0] != '0') {
+          op->d_coulomb = DevBuf<double>(coulomb_table_host());
+          reinterpret_cast<PlasmaParams<3> *>(op->params)->ctab = op->d_coulomb.get();
+        }
+      }
+      break;
     case 4: fill_plasma_params<4>(op, disc, phys, num_bcs, bcs); break;
     case 5: fill_plasma_params<5>(op, disc, phys, num_bcs, bcs); break;
     case 6: fill_plasma_params<6>(op, disc, phys, num_bcs, bcs); break;
@@ -1072,6 +1091,41 @@ int tpsrhs_math_eval(int function, int64_t n, const double *x, double *y) {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device visible");
     if (n > 0) {
       hipLaunchKernelGGL(k_math_eval, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, nullptr, function, n, x, y);
+      HIP_CHECK(hipGetLastError());
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+  });
+}
+
+namespace {
+// route 0: cfit_n; 1: the table with two wave-uniform rounds, then lane by lane; 2: lane by lane only.  1 / Tp^2 = 1.
+__global__ void k_coulomb_eval(int route, const double *tab, int64_t n, const double *__restrict__ x, double *__restrict__ out) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= n) return;
+  coll::Arg a;
+  a.ln = x[i];
+  a.inv2 = 1.0;
+  double g[8];
+  if (route == 0 || !coulomb::in_range(a.ln)) {
+    coll::cfit_tab<8>(nullptr, a, g);
+  } else if (route == 1) {
+    coll::ctab_eval<8, 2>(tab, a.ln, true, g);
+  } else {
+    coll::ctab_eval<8, 0>(tab, a.ln, true, g);
+  }
+#pragma unroll
+  for (int f = 0; f < 8; f++) out[f * n + i] = g[f];
+}
+}  // namespace
+
+int tpsrhs_coulomb_eval(int route, int64_t n, const double *x, double *out) {
+  if (route < 0 || route > 2 || n < 0 || !x || !out) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "coulomb_eval");
+  return guarded([&] {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device visible");
+    DevBuf<double> tab(coulomb_table_host());  // its own table, from the same fill as an operator's
+    if (n > 0) {
+      hipLaunchKernelGGL(k_coulomb_eval, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, nullptr, route, tab.get(), n, x, out);
       HIP_CHECK(hipGetLastError());
     }
     HIP_CHECK(hipDeviceSynchronize());
