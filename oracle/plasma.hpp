@@ -1029,6 +1029,7 @@ class SourceTerm {
     enableRadiation = p.radiation.model == TPSRHS_NET_EMISSION;
     if (enableRadiation) nec.init(p.radiation.nec_table);
   }
+  double energySink(double Th) const { return -4.0 * PI_ * nec.eval(Th); }  // NetEmission::computeEnergySink, src/radiation.hpp:68
   void point(const double *Uin, const double *Upin, const double *gradUpn, double *srcTerm) const {
     double upn[MAXEQ], Un[MAXEQ];
     for (int eq = 0; eq < num_equation; eq++) {
@@ -1060,7 +1061,7 @@ class SourceTerm {
       chemistry.computeCreationRate(progressRates, creationRates);
       for (int sp = 0; sp < numActiveSpecies; sp++) srcTerm[2 + nvel + sp] += creationRates[sp];
     }
-    if (enableRadiation) srcTerm[1 + nvel] += -4.0 * PI_ * nec.eval(Th);  // src/radiation.hpp:68
+    if (enableRadiation) srcTerm[1 + nvel] += energySink(Th);
     if (mixture->twoTemperature) {
       for (int r = 0; r < numReactions; r++)
         if (chemistry.isElectronInvolvedAt(r))

@@ -1239,6 +1239,80 @@ int tpsoracle_point_source_transport(void *h, const double *state, const double 
   op->transport->ComputeSourceTransportProperties(state, prim, gradUp, E, 0.0, global1, species, diffVel, n_sp);
   return 0;
 }
+// ---- point functions that exist to be compared with the reference's compiled code (oracle/ref_point.cpp) -------
+double tpsoracle_point_electron_pressure(void *h, const double *state) {
+  double pe = 0.0;
+  static_cast<Operator *>(h)->mixture->ComputePressure(state, &pe);
+  return pe;
+}
+int tpsoracle_point_species_primitives(void *h, const double *state, double *X, double *Y, double *n_sp) {
+  tpsoracle::PerfectMixture *pm = dynamic_cast<tpsoracle::PerfectMixture *>(static_cast<Operator *>(h)->mixture.get());
+  if (!pm) return 1;
+  pm->computeSpeciesPrimitives(state, X, Y, n_sp);
+  return 0;
+}
+int tpsoracle_point_species_enthalpies(void *h, const double *state, double *out) {
+  static_cast<Operator *>(h)->mixture->computeSpeciesEnthalpies(state, out);
+  return 0;
+}
+int tpsoracle_point_stagnation_state(void *h, const double *state, double *out) {
+  static_cast<Operator *>(h)->mixture->computeStagnationState(state, out);
+  return 0;
+}
+int tpsoracle_point_stagnant_state_with_temp(void *h, const double *state, double temp, double *out) {
+  static_cast<Operator *>(h)->mixture->computeStagnantStateWithTemp(state, temp, out);
+  return 0;
+}
+int tpsoracle_point_modify_energy_for_pressure(void *h, const double *state, double p, int modifyElectronEnergy,
+                                               double *out) {
+  static_cast<Operator *>(h)->mixture->modifyEnergyForPressure(state, out, p, modifyElectronEnergy != 0);
+  return 0;
+}
+int tpsoracle_point_modify_state_from_primitive(void *h, const double *state, const double *prim, const int *primIdxs,
+                                                double *out) {
+  tpsoracle::BoundaryPrimitiveData bc;
+  for (int i = 0; i < tpsoracle::MAXEQ; i++) {
+    bc.prim[i] = prim[i];
+    bc.primIdxs[i] = primIdxs[i] != 0;
+  }
+  static_cast<Operator *>(h)->mixture->modifyStateFromPrimitive(state, bc, out);
+  return 0;
+}
+int tpsoracle_point_sheath_bdr_flux(void *h, const double *state, double *primFlux) {
+  tpsoracle::BoundaryViscousFluxData bc;
+  for (int d = 0; d < 3; d++) bc.normal[d] = 0.0;
+  for (int i = 0; i < tpsoracle::MAXEQ; i++) {
+    bc.primFlux[i] = 0.0;
+    bc.primFluxIdxs[i] = false;
+  }
+  try {
+    static_cast<Operator *>(h)->mixture->computeSheathBdrFlux(state, bc);
+  } catch (const std::exception &e) {
+    g_err = e.what();
+    return 1;
+  }
+  for (int i = 0; i < tpsoracle::MAXEQ; i++) primFlux[i] = bc.primFlux[i];
+  return 0;
+}
+// the reaction part of the source: forward rate coefficients, equilibrium constants, progress and creation rates
+int tpsoracle_point_chemistry(void *h, const double *n_sp, double Th, double Te, double *kfwd, double *keq,
+                              double *progress, double *creation) {
+  Operator *op = static_cast<Operator *>(h);
+  if (!op->source) return 1;
+  const tpsoracle::Chemistry &c = op->source->chemistry;
+  c.computeForwardRateCoeffs(Th, Te, kfwd);
+  c.computeEquilibriumConstants(Th, Te, keq);
+  c.computeProgressRate(n_sp, kfwd, keq, progress);
+  c.computeCreationRate(progress, creation);
+  return 0;
+}
+// the radiation sink of the source (src/radiation.hpp:68), as SourceTerm::point adds it
+int tpsoracle_point_energy_sink(void *h, double Th, double *out) {
+  Operator *op = static_cast<Operator *>(h);
+  if (!op->source || !op->source->enableRadiation) return 1;
+  *out = op->source->energySink(Th);
+  return 0;
+}
 int tpsoracle_point_source(void *h, const double *state, const double *prim, const double *gradUp, double *src) {
   Operator *op = static_cast<Operator *>(h);
   if (!op->source) return 1;
