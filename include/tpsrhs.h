@@ -395,7 +395,11 @@ int tpsrhs_math_eval(int function, int64_t n, const double *x, double *y);
  * att12 .. att15 of src/collision_integrals.cpp:53-115) without their factor 1 / Tp^2, c0 log(1 + c1 e^(c2 x))^c3, at
  * n arguments x = ln Tp; out[f * n + i] (x, out: device pointers, synchronous).  Route 0: the formulas through the
  * device's exp / log; 1: the polynomial table of the 3-D p = 3 sweeps (tps_amd/csrc/coulomb_table.hpp) with wave-uniform
- * coefficient loads; 2: the same table read lane by lane.  Arguments off the table (and NaN) take route 0 in every route. */
+ * coefficient loads; 2: the same table read lane by lane; 3: the table through a window of two consecutive intervals in
+ * LDS that a 64-lane wave owns (the sweeps' route, which holds three or four): four one-wave blocks stride over the chunks of 64 arguments, chunk c
+ * goes to block c % 4, and a wave carries its window from one chunk to its next -- reloaded only when the lowest interval
+ * of the chunk is outside it; lanes above the window read lane by lane.  Arguments off the table (and NaN) take route 0 in
+ * every route.  Routes 1, 2 and 3 agree bit for bit. */
 int tpsrhs_coulomb_eval(int route, int64_t n, const double *x, double *out);
 
 int64_t tpsrhs_height(tpsrhs_handle h);

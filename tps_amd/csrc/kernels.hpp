@@ -218,6 +218,36 @@ template <class C, class PH>
 constexpr bool coulomb_tab() {
   return lean_one_hex<PH>::value && C::DIM == 3 && C::P == 3 && C::NC == 0;
 }
+// ... and which of them read that table through an LDS window of the wave (coll::Window) and how many intervals it holds:
+// k_gradient's one-hex face kernel (visc_phase_lean1; the general form keeps the per-lane route, the bits are the same) and
+// k_flux's nodal closure.  0: no window in that kernel.  What ships was chosen by measurement:
+// a wave whose lanes do not ALL fit the window runs both Horner chains, the LDS one and the global one, so the window has to
+// hold what a hex spans -- two intervals gain nothing, three do, four a little more in k_gradient and nothing in k_flux.
+#ifndef TPSRHS_COULOMB_WINDOW_GRAD
+#define TPSRHS_COULOMB_WINDOW_GRAD 4
+#endif
+// 1: k_gradient's window sits in the T chunk of the pool, which is dead between lean1_state_dir and lean1_grad_dir: no LDS of
+// its own (four intervals next to the pool would cost the third wave per SIMD), loaded anew by every closure.  0: an array
+// of its own that lives from one direction pair to the next.
+#ifndef TPSRHS_COULOMB_WINDOW_GRAD_POOL
+#define TPSRHS_COULOMB_WINDOW_GRAD_POOL 1
+#endif
+#ifndef TPSRHS_COULOMB_WINDOW_FLUX
+#define TPSRHS_COULOMB_WINDOW_FLUX 3
+#endif
+struct NoCoulombWindow {};
+template <class C, class PH, int W, bool ON_ = coulomb_tab<C, PH>() && (W > 0)>
+struct CoulombWin {  // the window of a kernel: its type (PlasmaPhys::CoulombWindow) and its LDS
+  static constexpr bool ON = false;
+  typedef NoCoulombWindow type;
+};
+template <class C, class PH, int W>
+struct CoulombWin<C, PH, W, true> {
+  static_assert(C::BLOCK == 64, "the window belongs to ONE wave: no workgroup barrier orders its loads and reads");
+  static constexpr bool ON = true;
+  typedef typename PH::template CoulombWindow<W> type;
+  static constexpr int DOUBLES = type::DOUBLES;
+};
 
 // LDS copy of the tables that are indexed per lane
 template <class C>
@@ -1894,11 +1924,11 @@ __device__ inline void lean1_state_dir(const double *sU, double *Tb, double *Wb,
   for (int k = 0; k < PH::NEQ; k++) u[k] = lean1_point<C>(Wb, k, bq, ll);
   block_sync<C::BLOCK>();
 }
-template <class C, class PH>
+template <class C, class PH, class CWIN>
 __device__ inline void visc_phase_lean1(const MeshDev &m, const int2 *sFI, typename PH::PRef prm0, int e0, const double *sU,
                                         const double *gradUp_q, bool node_on0, double *sJ, double *Tb, double *Wb,
                                         const double *sV, const Tab<C> &tab, const Tables1D &ct, double *__restrict__ TB,
-                                        int tid0 STAMP_PARAM) {
+                                        int tid0, const CWIN &win STAMP_PARAM) {
   constexpr int NEQ = PH::NEQ, DIM = C::DIM;
   static_assert(DIM == 3 && C::Q_ROUNDS == 1 && PH::NVEL == 3 && C::BLOCK == 64 && C::EPB == 1, "3-D, one wave = one hex");
   const bool node_on = __builtin_amdgcn_readfirstlane(node_on0) != 0;  // the same in every lane: a scalar branch
@@ -1958,7 +1988,12 @@ __device__ inline void visc_phase_lean1(const MeshDev &m, const int2 *sFI, typen
         double Us[NEQ];
         typename PH::WallFlux w;
         PH::visc_pass_state(pq, nb, pass, u, n, Us, w);
-        if constexpr (coulomb_tab<C, PH>())
+        if constexpr (!std::is_same<CWIN, NoCoulombWindow>::value) {
+          // (in the T chunk of the pool the window lives from lean1_state_dir to lean1_grad_dir only: it starts empty)
+          if constexpr (TPSRHS_COULOMB_WINDOW_GRAD_POOL) win.clear();
+          PH::template visc_point_lean<true>(pq, Us, w, cf, win);
+        }
+        else if constexpr (coulomb_tab<C, PH>())
           PH::template visc_point_lean<true>(pq, Us, w, cf);
         else
           PH::visc_point_lean(pq, Us, w, cf);
@@ -2254,9 +2289,19 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && PH::HEAVY) ? 1 : PH::minw_grad(
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const double *gq = gradUp;
     const unsigned node = static_cast<unsigned>(e0 + le_n) * C::NPE + nd;
-    if constexpr (PH::LEAN_ONE_HEX && C::EPB == 1 && C::BLOCK % C::LN == 0 && !TPSRHS_LEAN_GENERAL)
-      visc_phase_lean1<C, PH>(m, sFI, prm, e0, sU, gq, node_on, sJ, sUp, sW, sV, tab, ct, TB, tid STAMP_ARG);
-    else
+    if constexpr (PH::LEAN_ONE_HEX && C::EPB == 1 && C::BLOCK % C::LN == 0 && !TPSRHS_LEAN_GENERAL) {
+      // the window of the Coulomb table (TPSRHS_COULOMB_WINDOW_GRAD_POOL above)
+      typedef CoulombWin<C, PH, TPSRHS_COULOMB_WINDOW_GRAD> CW;
+      typename CW::type win;
+      if constexpr (CW::ON && TPSRHS_COULOMB_WINDOW_GRAD_POOL) {
+        static_assert(CW::DOUBLES <= L::SUP, "the window takes the T chunk of the pool");
+        win.create(sUp, prm.cwin != 0);
+      } else if constexpr (CW::ON) {
+        __shared__ __attribute__((aligned(16))) double sCw[CW::DOUBLES];
+        win.create(sCw, prm.cwin != 0);
+      }
+      visc_phase_lean1<C, PH>(m, sFI, prm, e0, sU, gq, node_on, sJ, sUp, sW, sV, tab, ct, TB, tid, win STAMP_ARG);
+    } else
       visc_phase_lean3d<C, PH>(m, sFI, prm, e0, sU, gq, node_on, node, sJ, sUp, sW, sV, tab, ct, TB, tid STAMP_ARG);
     STAMP_FLUSH();
     return;
@@ -2957,7 +3002,14 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && (PH::HEAVY || PH::MINW_FLUX > 2
       const typename PH::State st = PH::make_state(prm, uc);
       speed = PH::max_char_speed(prm, uc, st);
       typename PH::FluxCoef fc;
-      if constexpr (coulomb_tab<C, PH>())
+      if constexpr (CoulombWin<C, PH, TPSRHS_COULOMB_WINDOW_FLUX>::ON) {
+        // the window of the Coulomb table: an array of its own (the pool takes the next stage's traces in the RK epilogue)
+        typedef CoulombWin<C, PH, TPSRHS_COULOMB_WINDOW_FLUX> CW;
+        __shared__ __attribute__((aligned(16))) double sCw[CW::DOUBLES];
+        typename CW::type win;
+        win.create(sCw, prm.cwin != 0);
+        PH::template flux_coeffs<true>(prm, uc, st, fc, win);
+      } else if constexpr (coulomb_tab<C, PH>())
         PH::template flux_coeffs<true>(prm, uc, st, fc);
       else if constexpr (PH::TWO_STEP)
         PH::flux_coeffs(prm, uc, st, fc);

@@ -92,6 +92,9 @@ struct PlasmaParams {
   // coulomb_table.hpp: the eight Coulomb fits of the third-order k_e as piecewise polynomials in ln Tp, device memory of the
   // operator; NULL: the formulas.  Read only by the closures compiled with CTAB (3-D, p = 3, argon-minimal ternary).
   const double *ctab;
+  // the sweeps read the table through an LDS window of the wave (coll::Window) where they are compiled with one; 0: lane by
+  // lane (TPSRHS_COULOMB_WINDOW=0 at operator creation: the A/B switch within one library)
+  int cwin;
 };
 
 __device__ inline double ipow(double x, int k) {  // pow(x, small non-negative integer), pow(0,0) = 1
@@ -267,6 +270,96 @@ __device__ inline void cfit_tab(const double *tab, const Arg &a, double (&out)[N
     out[1] = rep22(a);
   }
 }
+#if defined(__HIPCC__)
+#ifndef TPSRHS_COULOMB_WINDOW_W
+#define TPSRHS_COULOMB_WINDOW_W 2  // intervals of the probe's window (tpsrhs_coulomb_eval, route 3)
+#endif
+// The third route, device code only: W consecutive intervals of the table in LDS, owned by ONE wave (a one-wave block).  The
+// lanes of a hex ask for two or three intervals; through the window they read them with ds_read_b128 (identical addresses
+// broadcast) instead of 40 global_load_dwordx4 per lane.  The window's base interval is kept in LDS behind the coefficients:
+// the evaluation sits inside divergent control flow, where a register copy would go stale in the lanes that are switched off.
+// The window relies on the LDS executing one wave's DS instructions in issue order plus a compiler fence (wave_fence), and
+// on no workgroup barrier.  `on` is PlasmaParams::cwin (uniform): off, every lane takes the per-lane route.
+__device__ inline void wave_fence() {  // (kernels.hpp::block_sync<64>)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+template <int W_>
+struct Window {
+  static_assert(W_ >= 1 && W_ <= coulomb::NI, "intervals of the table");
+  static constexpr int W = W_;
+  static constexpr int COEF = W_ * coulomb::STRIDE;
+  static constexpr int DOUBLES = COEF + 2;  // the coefficients, then the base interval (an int in a 16-byte slot)
+  typedef double __attribute__((address_space(3))) *Lds;
+  Lds lds;
+  bool on;
+  // `mem`: DOUBLES doubles of LDS, 16-byte aligned, that nothing else writes while the window lives.  The window starts
+  // empty; `clear` empties it again (after something else has used its LDS).
+  __device__ inline void create(double *mem, bool enabled) {
+    lds = (Lds)mem;
+    on = enabled;
+    clear();
+  }
+  __device__ inline void clear() const {  // (any lanes: they all write the same)
+    wave_fence();
+    *reinterpret_cast<int __attribute__((address_space(3))) *>(lds + COEF) = -2 * coulomb::NI;
+    wave_fence();
+  }
+};
+// ctab_eval through the window, called by the lanes whose x is on the table (and by no other: what is computed across the
+// wave below is defined by the ACTIVE lanes alone).  The lowest interval of the active lanes decides: if the window holds
+// it, nothing is loaded; otherwise the active lanes copy W intervals from it on (clamped at the table's end) in 16-byte
+// pieces, piece = rank among the active lanes, stride = their number.  Lanes whose interval the window holds run horner on
+// the LDS pointer, the others on the global one: the same coefficients, the same FMA order, the same bits.
+template <int NF, class WIN>
+__device__ inline void ctab_window_eval(const WIN &win, const double *tab, double x, double (&g)[NF]) {
+  const int idx = coulomb::interval(x);
+  const double t = coulomb::local(x, idx);
+  int rel = -1;
+  if (win.on) {
+    const unsigned long long act = __ballot(1);
+    int lo = __builtin_amdgcn_readfirstlane(idx);
+    for (;;) {  // one trip per distinct interval below the first lane's
+      const unsigned long long below = __ballot(idx < lo);
+      if (below == 0) break;
+      lo = __builtin_amdgcn_readlane(idx, static_cast<int>(__builtin_ctzll(below)));
+    }
+    int __attribute__((address_space(3))) *bp = reinterpret_cast<int __attribute__((address_space(3))) *>(win.lds + WIN::COEF);
+    wave_fence();
+    int base = __builtin_amdgcn_readfirstlane(*bp);
+    if (lo < base || lo >= base + WIN::W) {
+      base = lo < coulomb::NI - WIN::W ? lo : coulomb::NI - WIN::W;
+      const int rank = static_cast<int>(__builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(act >> 32),
+                                                                  __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(act), 0u)));
+      const int step = __builtin_popcountll(act);
+      typedef double __attribute__((ext_vector_type(2))) d2;
+      const d2 *src = reinterpret_cast<const d2 *>(tab + base * coulomb::STRIDE);
+      d2 __attribute__((address_space(3))) *dst = reinterpret_cast<d2 __attribute__((address_space(3))) *>(win.lds);
+      for (int pc = rank; pc < WIN::COEF / 2; pc += step) dst[pc] = src[pc];
+      if (rank == 0) *bp = base;
+      wave_fence();
+    }
+    rel = idx - base;
+  }
+  if (rel >= 0 && rel < WIN::W)
+    coulomb::horner<NF>(static_cast<const double __attribute__((address_space(3))) *>(win.lds) + rel * coulomb::STRIDE, t, g);
+  else
+    coulomb::horner<NF>(tab + idx * coulomb::STRIDE, t, g);
+}
+// cfit_tab with a window (coll::Window)
+template <int NF, class WIN>
+__device__ inline void cfit_tab(const double *tab, const Arg &a, double (&out)[NF], const WIN &win) {
+  static_assert(TPSRHS_COULOMB_UNIFORM == 0, "the window replaces the per-lane route");
+  if (tab != nullptr && coulomb::in_range(a.ln)) {
+    ctab_window_eval<NF>(win, tab, a.ln, out);
+#pragma unroll
+    for (int f = 0; f < NF; f++) out[f] *= a.inv2;
+  } else {
+    cfit_tab<NF>(nullptr, a, out);
+  }
+}
+#endif
 #endif
 // Coulomb fits by (attractive 0 / repulsive 1, l, r): c0, c1, c2, c3 (src/collision_integrals.cpp:53-115);
 // rows the reference does not have are zero
@@ -370,6 +463,10 @@ struct PlasmaPhys {
   // one-hex form where the block is one hex (kernels.hpp::visc_phase_lean1: lane offsets once per face direction, round 5).
   // The other ternary instantiations keep the general form token for token: a third of them sit on the spill allow-list.
   static constexpr bool LEAN_ONE_HEX = LEAN_TRACE && !TWOT && TRANSPORT == TRANSPORT_ARGON_MINIMAL;
+#if defined(TPSRHS_HAVE_COULOMB_TABLE) && defined(__HIPCC__)
+  template <int W>
+  using CoulombWindow = coll::Window<W>;  // kernels.hpp::CoulombWin
+#endif
   static constexpr bool LAUNDER_FLUX = false;  // k_flux re-fetches the parameter image where its face term starts (the table gas)
   static constexpr int minw_grad(int dim, int p, int nc) {
     return (LEAN_TRACE && dim == 3 && !nc && p <= 3) ? TPSRHS_PLASMA_MINW_GRAD_LEAN : MINW_GRAD;
@@ -708,12 +805,15 @@ struct PlasmaPhys {
   // Results differ from the reference's order by rounding (a few ulp).
   // CTAB: the Coulomb fits of the argon-minimal ternary closure from the polynomial table p.ctab (coll::cfit_tab) -- the
   // sweeps of the 3-D p = 3 collocated operator only (kernels.hpp::coulomb_tab); every other caller keeps the formulas.
-  template <bool CTAB = false>
+  // win: nothing, or the wave's LDS window of that table (coll::Window) -- a parameter pack, so that without a window the
+  // function is, parameter for parameter, what it was before there were windows (no other instantiation's code moves).
+  template <bool CTAB = false, class... WIN>
   __device__ static inline void transport_coeffs(PRef p, const double *U, double Th, double Te, bool diffusion,
-                                                 TCoef &t) {
+                                                 TCoef &t, const WIN &...win) {
 #ifndef TPSRHS_HAVE_COULOMB_TABLE
     static_assert(!CTAB, "coulomb_table.hpp is not part of this build");
 #endif
+    static_assert(sizeof...(WIN) <= (CTAB ? 1 : 0), "at most one window, and only of the table");
     static_assert(!CTAB || (!TWOT && TRANSPORT == TRANSPORT_ARGON_MINIMAL), "the table serves the single-temperature argon-minimal closure");
     const Species q = species(p, U);
 #pragma unroll
@@ -823,7 +923,7 @@ struct PlasmaPhys {
 #ifdef TPSRHS_HAVE_COULOMB_TABLE
         if constexpr (CTAB) {
           double g[8];
-          coll::cfit_tab<8>(p.ctab, d.e, g);
+          coll::cfit_tab<8>(p.ctab, d.e, g, win...);
 #pragma unroll
           for (int f = 0; f < 4; f++) {
             A[f] = g[f];
@@ -847,7 +947,7 @@ struct PlasmaPhys {
 #ifdef TPSRHS_HAVE_COULOMB_TABLE
         if constexpr (CTAB) {  // (single-temperature: d.h is d.e) the rows att11 and rep22 of the table alone
           double g[2];
-          coll::cfit_tab<2>(p.ctab, d.e, g);
+          coll::cfit_tab<2>(p.ctab, d.e, g, win...);
           Qatt = g[0] * d.circle;
           rep22h = g[1] * d.circle;
         } else
@@ -1111,10 +1211,10 @@ struct PlasmaPhys {
   }
   // closure of the nodal flux: everything of ComputeFluxTransportProperties that depends on the state alone
   typedef TCoef FluxCoef;
-  template <bool CTAB = false>
-  __device__ static inline void flux_coeffs(PRef p, const double *U, const State &s, FluxCoef &c) {
+  template <bool CTAB = false, class... WIN>
+  __device__ static inline void flux_coeffs(PRef p, const double *U, const State &s, FluxCoef &c, const WIN &...win) {
     if (p.eq_system == TPSRHS_EULER) return;
-    transport_coeffs<CTAB>(p, U, s.Th, s.Te, true, c);
+    transport_coeffs<CTAB>(p, U, s.Th, s.Te, true, c, win...);
   }
   __device__ static inline void total_flux(PRef p, const double *U, const State &s, const FluxCoef &c,
                                            const double *g, double radius, double *F, const EddyCtx &ec = eddy_off()) {
@@ -1538,11 +1638,11 @@ struct PlasmaPhys {
     double hf0, ef0, sf0[NACTIVE];                 // prescribed (wall) parts of the heavy / electron heat flux and species rows
     double hfc[NIN], efc[NIN], sfc[NACTIVE][NIN];  // the same three as linear maps of the inputs
   };
-  template <bool CTAB = false>
-  __device__ static inline void visc_point_lean(PRef p, const double *U, const WallFlux &w, ViscLean &L) {
+  template <bool CTAB = false, class... WIN>
+  __device__ static inline void visc_point_lean(PRef p, const double *U, const WallFlux &w, ViscLean &L, const WIN &...win) {
     const State s = make_state(p, U);
     TCoef t;
-    transport_coeffs<CTAB>(p, U, s.Th, s.Te, !w.species, t);
+    transport_coeffs<CTAB>(p, U, s.Th, s.Te, !w.species, t, win...);
     double h[NSP];
     enthalpies(p, s, h);
     L.mu = t.visc;

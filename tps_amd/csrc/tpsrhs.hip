@@ -143,6 +143,9 @@ void fill_mixture_params(tpsrhs_operator *op, const OperatorPlan &pl, const tpsr
         if (!env || env[0] != '0') {
           op->d_coulomb = DevBuf<double>(coulomb_table_host());
           reinterpret_cast<PlasmaParams<3> *>(op->params)->ctab = op->d_coulomb.get();
+          // TPSRHS_COULOMB_WINDOW=0: every lane reads its own coefficients (the same kind of switch for the LDS window)
+          const char *win = std::getenv("TPSRHS_COULOMB_WINDOW");
+          reinterpret_cast<PlasmaParams<3> *>(op->params)->cwin = (!win || win[0] != '0') ? 1 : 0;
         }
       }
       break;
@@ -1118,13 +1121,21 @@ __global__ void k_coulomb_eval(int route, const double *tab, int64_t n, const do
 }
 }  // namespace
 
+// route 3, the LDS window of a wave: coulomb_probe.hip (a unit of its own -- a kernel added to this one renumbers the labels of
+// every kernel the compiler emits after it, and the device code of this unit is compared from commit to commit)
+// (C++ linkage: this declaration stands inside an extern "C" block)
+extern "C++" void coulomb_probe_window(const double *tab, int64_t n, const double *x, double *out);
+
 int tpsrhs_coulomb_eval(int route, int64_t n, const double *x, double *out) {
-  if (route < 0 || route > 2 || n < 0 || !x || !out) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "coulomb_eval");
+  if (route < 0 || route > 3 || n < 0 || !x || !out) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "coulomb_eval");
   return guarded([&] {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device visible");
     DevBuf<double> tab(coulomb_table_host());  // its own table, from the same fill as an operator's
-    if (n > 0) {
+    if (n > 0 && route == 3) {
+      coulomb_probe_window(tab.get(), n, x, out);
+      HIP_CHECK(hipGetLastError());
+    } else if (n > 0) {
       hipLaunchKernelGGL(k_coulomb_eval, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, nullptr, route, tab.get(), n, x, out);
       HIP_CHECK(hipGetLastError());
     }
