@@ -9,8 +9,13 @@ the failing call out, and all ten cycles must agree: a cycle with the failed cal
 The drift of the free device memory between cycle 2 and cycle 10 is printed, not asserted: the card may be shared.
 Second case: the loader of the kernel families (TPSRHS_FAMILY_PATH) skips a directory without the family and refuses a
 shared object that is no family of this build.
+Third case: the operator owns its post-processing state as well (statistics, samplers and probe records, the monitor, the
+samplers tpsrhs_transfer caches on the source): four cycles of a destination and a source operator that use all of it and
+are destroyed in either order read the same bytes, in this process and under TPSRHS_POISON=1 in a fresh one.  The drift
+of the free device memory is printed as in the first case, which sets no bound on it (the card may be shared).
 
-Run as a program (the child process of the poisoned case) it prints the digest of the final state of each workload."""
+Run as a program (the child process of the poisoned cases) it prints the digest of the final state of each workload, or,
+with the argument `observers`, the digest of the third case."""
 import hashlib
 import os
 import subprocess
@@ -133,6 +138,87 @@ def test_ten_cycles_with_poisoned_allocations():
     assert r.stdout.count("LIFECYCLE SAME") == 2
 
 
+def _observers_cycle(side, destination_first):
+    """two operators, every kind of post-processing state on them, three steps; returns the bytes of everything read"""
+    import torch
+    from tps_amd.rhs_operator import RHSoperator
+
+    def box(order):  # 2 x 2 x 2 hexahedra, dry air, Navier-Stokes, isothermal walls all round
+        mesh = meshgen.box_hex(2, 2, 2, periodic=(False, False, False), bdr_attr={(d, e): 3 for d in range(3) for e in (0, 1)})
+        return cases.Case(f"observers_p{order}", mesh, capi.Disc(order, 0, 0, 0, 0), capi.dry_air_physics(capi.NS),
+                          [capi.make_bc(3, capi.WALL, capi.VISC_ISOTH, [300.0])])
+
+    out = []
+    with torch.cuda.stream(side):
+        cd, cs = box(1), box(2)
+        dst = RHSoperator(cd.mesh, cd.disc, cd.physics, cd.bcs, stream=side)
+        src = RHSoperator(cs.mesh, cs.disc, cs.physics, cs.bcs, stream=side)
+        x = torch.tensor(np.ascontiguousarray(cd.state(seed=7)).ravel(), dtype=torch.float64, device=dst.device)
+        xs = torch.tensor(np.ascontiguousarray(cs.state(seed=8)).ravel(), dtype=torch.float64, device=src.device)
+        dst.configureStatistics(1, 0, variances=True)
+        dst.configureStatistics(1, 0, variances=True)  # reconfigured: the first state goes, with its fields
+        pts = np.array([[0.3, 0.7, 2.0], [0.2, 0.6, 2.0], [0.4, 0.9, 2.0]])  # (dim, npts): the third lies outside the box
+        sampler = dst.createSampler(pts, fill=-1.0)
+        dst.configureProbes(sampler, 1, 2)  # three steps into two rows: the third record is dropped
+        dst.configureMonitor(1, 4)
+        moved, missing = dst.transferFrom(src, xs)  # locates the p = 1 nodes in the p = 2 operator and keeps the sampler there
+        assert missing == 0 and src.transferStats() == (1, 0)
+        out.append(moved.cpu().numpy().tobytes())
+        time, dt, bad = dst.advance(x, 0.0, 1e-9, 3, True, integrator="forwardEuler")
+        assert bad == 0
+        mean, vari, ns_mean, ns_vari, it = dst.getStatistics()
+        assert (ns_mean, ns_vari, it) == (3, 3, 3)
+        out += [mean.cpu().numpy().tobytes(), vari.cpu().numpy().tobytes()]
+        elem, ref, nfound = sampler.info()
+        assert nfound == 2 and elem[2] == -1
+        out += [elem.tobytes(), ref.tobytes(), sampler.sample(x).cpu().numpy().tobytes()]
+        iters, times, values, ndropped = dst.readProbes()
+        assert list(iters) == [1, 2] and ndropped == 1
+        out += [times.tobytes(), values.tobytes()]
+        mon = dst.readMonitor()
+        assert list(mon["iters"]) == [1, 2, 3] and mon["ndropped"] == 0
+        out += [mon[k].tobytes() for k in ("times", "dts", "totals", "mins", "maxs")]
+        out += [x.cpu().numpy().tobytes(), np.array([time, dt]).tobytes()]
+        side.synchronize()
+        for op in ((dst, src) if destination_first else (src, dst)):
+            op.close()
+    for b in out[:3] + out[4:]:  # (out[3]: the elements, integers)
+        assert np.all(np.isfinite(np.frombuffer(b)))
+    return b"".join(out)
+
+
+OBSERVER_CYCLES = 4
+
+
+def _observer_cycles():
+    """the one digest of OBSERVER_CYCLES cycles; the odd cycles destroy the destination first, the even ones the source"""
+    import torch
+
+    side = torch.cuda.Stream()
+    first, free1 = None, 0
+    for k in range(1, OBSERVER_CYCLES + 1):
+        digest = hashlib.sha256(_observers_cycle(side, destination_first=k % 2 == 1)).hexdigest()
+        first = first or digest
+        assert digest == first, f"cycle {k} differs from cycle 1"
+        if k == 1:
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            free1 = torch.cuda.mem_get_info()[0]
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    print(f"lifecycle observers: digest {first} free-memory drift cycle 1 -> {OBSERVER_CYCLES}: {free1 - torch.cuda.mem_get_info()[0]} bytes")
+    return first
+
+
+def test_post_processing_state_goes_with_its_operator_in_either_order():
+    digest = _observer_cycles()
+    env = dict(os.environ, TPSRHS_POISON="1")
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "observers"], capture_output=True, text=True, env=env, timeout=300)
+    print(r.stdout[-2000:])
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert f"OBSERVERS {digest}" in r.stdout
+
+
 def _family_case(stranger, empty):
     """in a process that has loaded no kernel family yet (a loaded one is kept, and the search is not repeated)"""
     import torch
@@ -174,6 +260,9 @@ def test_family_path_is_searched_and_strangers_are_refused(tmp_path):
 if __name__ == "__main__":
     if sys.argv[1:2] == ["family"]:
         _family_case(sys.argv[2], sys.argv[3])
+        sys.exit(0)
+    if sys.argv[1:2] == ["observers"]:
+        print("OBSERVERS", _observer_cycles())
         sys.exit(0)
     for kind in ("box", "cylinder_nr"):
         first, last, _ = _ten_cycles(kind)

@@ -1,6 +1,6 @@
 // PROBE build (not shipped): only the instantiation that tools/sweep_instantiations.py found wrong in round 3 --
 // 3-D, Gauss-Lobatto pair, p = 1, seven species, not ambipolar, single temperature, argon mixture transport.
-#include "../operator.hpp"
+#include "../launch.hpp"
 #include "../physics_plasma.hpp"
 
 extern "C" int pick_plasma_3d_n7(tpsrhs_operator *op, int two_temperature, int transport, char *, int) {

@@ -1,0 +1,84 @@
+// What the units of the C ABI share besides the operator (operator.hpp) and the statuses (status.hpp: fail, guarded, the
+// last error): the dispatch over (dim, order), the read-back of a record log, and the few functions that cross from one
+// unit to another -- plain C++ functions inside the library, as pick_dryair_axisym is.  No kernel in here.
+#ifndef TPSRHS_ABI_SUPPORT_HPP_
+#define TPSRHS_ABI_SUPPORT_HPP_
+
+#include <type_traits>
+
+#include "operator.hpp"
+#include "record_log.hpp"
+
+namespace tpsrhs {
+struct TableDev;  // physics_plasma.hpp
+}
+
+// ---- tpsrhs.hip
+// LinearTable::LinearTable (src/table.cpp:39-50): interval coefficients (plasma_params_host.hpp), uploaded with the
+// abscissae into a buffer that `owner` keeps
+tpsrhs::TableDev upload_table(std::vector<DevBuf<void>> &owner, const tpsrhs_table &t);
+// the polynomial table of the Coulomb fits (coulomb_table.hpp), filled once per process from the literals of the closure
+const std::vector<double> &coulomb_table_host();
+
+// ---- the observers of the device time loop (time_loop.hip: after_step / work_due_after_next).  The loop knows each by its
+// StepCadence (record_log.hpp; NULL: not configured, interval 0: off) and by the function that does its work on the
+// operator's stream once the cadence says so.
+tpsrhs::StepCadence *stats_cadence(tpsrhs_operator *h);    // statistics.hip
+void stats_sample(tpsrhs_operator *h, const double *x);
+tpsrhs::StepCadence *probe_cadence(tpsrhs_operator *h);    // sampling.hip
+void probe_record(tpsrhs_operator *h, const double *x);
+tpsrhs::StepCadence *monitor_cadence(tpsrhs_operator *h);  // integrals.hip
+void monitor_record(tpsrhs_operator *h, const double *x);
+
+// ---- sampling.hip
+// h is being destroyed: tpsrhs_transfer forgets it as a source and drops every cached sampler at its nodes (the cache is
+// keyed by the address of the destination, which the next tpsrhs_create may hand out again)
+void transfer_forget(tpsrhs_operator *h);
+
+// {dt, time, max speed} of the time loop in device memory; the probe and monitor records copy the time from there
+inline double *loop_ctl(tpsrhs_operator *h) {
+  if (!h->loop.d_ctl) h->loop.d_ctl = DevBuf<double>(3);
+  return h->loop.d_ctl.get();
+}
+
+// the entry points that take no operator: there is no CPU path
+inline void require_device(const char *what = "no HIP device visible") {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw NoDevice(what);
+}
+
+// f(std::integral_constant<int, DIM>, std::integral_constant<int, P>) for the operator's dim and order: the (dim, order) pairs
+// the post-processing kernels are built for, listed once
+template <int N>
+using int_c = std::integral_constant<int, N>;
+template <class F>
+void with_dim_order(const tpsrhs_operator *h, const char *who, F &&f) {
+  switch (h->dim * 10 + h->order) {
+    case 21: f(int_c<2>(), int_c<1>()); break;
+    case 22: f(int_c<2>(), int_c<2>()); break;
+    case 23: f(int_c<2>(), int_c<3>()); break;
+    case 24: f(int_c<2>(), int_c<4>()); break;
+    case 25: f(int_c<2>(), int_c<5>()); break;
+    case 31: f(int_c<3>(), int_c<1>()); break;
+    case 32: f(int_c<3>(), int_c<2>()); break;
+    case 33: f(int_c<3>(), int_c<3>()); break;
+    case 34: f(int_c<3>(), int_c<4>()); break;
+    case 35: f(int_c<3>(), int_c<5>()); break;
+    default: throw Unsupported(std::string(who) + ": dim 2 or 3 and polynomial orders 1..5 are built");
+  }
+}
+
+// What reading the probe records and reading the monitor records share.  The first n rows of one column of a log (`width`
+// doubles a row) to the host, on the operator's stream ...
+inline void fetch_rows(tpsrhs_operator *h, double *dst, const DevBuf<double> &col, int64_t n, int64_t width) {
+  if (dst && n * width) HIP_CHECK(hipMemcpyAsync(dst, col.get(), sizeof(double) * n * width, hipMemcpyDeviceToHost, h->stream));
+}
+// ... and, once the stream has been synchronised, the host half: the counters, the step of every record, the optional restart
+inline void read_index(RecordIndex &ix, int64_t *nrecords, int64_t *ndropped, int64_t *iters_out, int reset) {
+  if (nrecords) *nrecords = ix.nrecords;
+  if (ndropped) *ndropped = ix.ndropped;
+  if (iters_out && ix.nrecords) std::memcpy(iters_out, ix.iters.data(), sizeof(int64_t) * ix.nrecords);
+  if (reset) ix.reset();  // the buffer starts again; the step counter goes on
+}
+
+#endif

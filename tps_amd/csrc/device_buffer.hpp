@@ -1,4 +1,4 @@
-// Device memory of the library: HIP_CHECK, the one allocator (dev_alloc, which TPSRHS_POISON fills) and
+// Device memory of the library: HIP_CHECK (which throws status.hpp's DeviceError), the one allocator (dev_alloc, which TPSRHS_POISON fills) and
 // DevBuf<T>, device memory with an owner -- freed by the destructor, move-only.  A DevBuf knows neither its size nor a
 // stream nor a device: whoever lets one go while a kernel may still read it synchronises first, on the device that holds
 // it.  DevBuf<void> owns a buffer whose element type no longer matters (the operator's bags of tables and parameter
@@ -15,17 +15,15 @@
 #include <string>
 #include <vector>
 
-namespace {
+#include "status.hpp"
 
-struct DeviceError : std::runtime_error {
-  explicit DeviceError(const std::string &s) : std::runtime_error(s) {}
-};
+namespace {
 
 #define HIP_CHECK(expr)                                                                                   \
   do {                                                                                                    \
     hipError_t _e = (expr);                                                                               \
     if (_e != hipSuccess)                                                                                 \
-      throw DeviceError(std::string(#expr) + ": " + hipGetErrorString(_e) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"); \
+      throw tpsrhs::DeviceError(std::string(#expr) + ": " + hipGetErrorString(_e) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"); \
   } while (0)
 
 // TPSRHS_POISON=1 (debug / tests/test_gpu_poison.py): every device allocation of the library starts as all-ones bytes

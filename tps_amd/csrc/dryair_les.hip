@@ -1,6 +1,6 @@
 // Kernel instantiations of dry air with the sub-grid scale models and the planar viscous sponge of the reference's
 // Fluxes (src/fluxes.cpp:223-246, 513-688): planar 2-D and 3-D, Gauss-Legendre pair (collocated kernels only).
-#include "operator.hpp"
+#include "launch.hpp"
 #include "physics_dryair.hpp"
 
 template <int DIM>

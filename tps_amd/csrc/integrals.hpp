@@ -1,7 +1,7 @@
 // Reductions over a byNODES DG field on the device: volume integrals and L2 errors (tpsrhs_integrate: what the reference
 // prints from M2ulPhyS::checkSolutionError through GridFunction::ComputeLpError, src/masa_handler.cpp:139-152), the range
 // of every row and the mean |value| (tpsrhs_nodal_stats: RHSoperator::computeMeanTimeDerivatives, src/rhs_operator.cpp:833-849),
-// and the monitor records the device time loop keeps of them.  Included by tpsrhs.hip only: the kernel families do not see
+// and the monitor records the device time loop keeps of them.  Included by integrals.hip only: the kernel families do not see
 // it.  The rule and its host half are quadrature_points.hpp.
 //
 // Summation structure (the contract of include/tpsrhs.h): the terms of one element are summed first, the element sums of
@@ -40,7 +40,7 @@ struct tpsrhs_monitor_log {
   DevBuf<double> d_totals, d_mins, d_maxs;  // [capacity][neq]
 };
 
-// behind tpsrhs_operator::integrals; owned by tpsrhs.hip (created at the first use, freed by tpsrhs_destroy)
+// behind tpsrhs_operator::integrals; created by integrals.hip at the first use, owned by the operator
 struct tpsrhs_integrals_state {
   int integ_blocks = 0, integ_run = 0, integ_eb = 1;  // grid, elements per block (a multiple of integ_eb), segments
   int stat_blocks = 0, stat_run = 0, stat_lpe = 64;

@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "basis.hpp"
+#include "kernel_args.hpp"
 #include "physics_dryair.hpp"
 
 namespace tpsrhs {
@@ -257,67 +258,6 @@ struct Tab {
   double xv[C::QV], wv[C::QV];  // volume rule (read by the non-collocated variant)
 };
 
-// ConstantPressureGradient / HeatSource / SpongeZone / JouleHeating of RHSoperator's forcing array
-// (src/rhs_operator.cpp:101-166), evaluated per node in k_flux next to the point sources.  One block in
-// device memory; the address is wave-uniform, so its fields arrive through scalar loads.
-struct ForcingDev {
-  int has_pg, nheat, nsponge, pad;
-  double pg[3];
-  struct Heat {
-    double value, radius, len;  // len = |point2 - point1|
-    double p1[3], axis[3];      // axis = unit vector point1 -> point2
-  } heat[TPSRHS_MAXHEATSOURCES];
-  struct Sponge {
-    int type, pad;
-    double normal[3], p0[3], pinit[3];
-    double r1, r2, mult;
-    double target[TPSRHS_MAXEQUATIONS];
-    // mixed-out target (SpongeZoneSolution::MIXEDOUT): nodes of the mix-out plane, and the sums over them
-    int mixed_out, n_plane;
-    const int *plane_nodes;  // [n_plane] device
-    double *msum;            // [NEQ + 1] device: sum of F_c . n per equation, number of nodes
-  } sponge[TPSRHS_MAXSPONGEZONES];
-  const double *joule;  // [ndofs] or NULL
-  int nps, pad2;
-  struct Scalar {
-    double x0[3], radius, value;
-  } ps[TPSRHS_MAXPASSIVESCALARS];
-};
-
-// RK4 stage combination fused into the epilogue of k_flux inside tpsrhs_rk4_step / tpsrhs_advance (src/M2ulPhyS.cpp:
-// 2004-2008 around MFEM's RK4Solver::Step): the residual k of a node never goes to memory, the lane that owns the node
-// writes the next stage's state (or the new solution) instead.
-//   mode 0  plain Mult: Y = k
-//   mode 1  out = U + dt/2 k           (stage 1: the stage input is x itself, taken from LDS)
-//   mode 2  out = x0 + dt/2 k          mode 3  out = x0 + dt k
-//   mode 4  out = x0 + [(y2 - x0) + 2 (y3 - x0) + (y4 - x0)] / 3 + dt/6 k,  then the NaN census and the species clamp
-//           (Check_NAN, Check_Undershoot).  With y2 = x0 + dt/2 k1, y3 = x0 + dt/2 k2, y4 = x0 + dt k3 this is
-//           x0 + dt/6 (k1 + 2 k2 + 2 k3 + k4): the accumulator z of RK4Solver::Step is recovered from the stage states
-//           instead of being streamed through memory at every stage (6 vector passes per step instead of 14); the
-//           differences are exact, the result differs from the reference's order of operations by rounding only.
-struct RkDev {
-  int mode, sp_first, sp_last, pad;
-  double dt_host;
-  const double *dt_dev;  // tpsrhs_advance keeps dt in device memory
-  const double *x0, *y2, *y3, *y4;
-  double *out;
-  unsigned long long *nan_count;
-  double *ta_out;  // non-NULL (stages 1..3 of a step, launch_all): the face-node traces of `out` go here -- the NEXT stage's
-                   // k_traces sweep done where the new state sits in registers (3-D collocated kernels, flux_fuses_traces)
-};
-
-struct MeshDev {
-  const int *blocks;           // workgroup -> block of EPB consecutive elements (NULL: identity); lets one
-                               // launch cover the interior and another the blocks that touch shared faces
-  int ne;
-  int reverse;                 // 1: the sweep walks each XCD's chunk of the block list backwards (xcd_block)
-  int64_t ndofs;
-  const double *verts;         // [ne][NV][DIM] lexicographic corners
-  const int2 *face_info;       // [ne*NFACES] {neighbour slot | -(bc+1), orientation code}
-  const double *minv;          // non-collocated variant: [ne][NPE][NPE] inverse element mass matrices (symmetric)
-  MixLenDev ml;                // MixingLengthTransport (2-D kernels): wall-distance grid function, or distance = NULL
-  VsDev vs;                    // viscous sponge of the 2-D kernels with the heavy interface (enabled = 0: none)
-};
 // what the closures of the 2-D heavy kernels take of the mixing-length model and the viscous sponge at one point
 // (`park`: the block's LDS array of sponge weights, one word per lane -- see EddyCtx::vsw)
 __device__ inline EddyCtx closure_ctx(const MeshDev &m, bool dist_on, double dist, const double *X, double *park) {
@@ -339,7 +279,7 @@ __device__ inline int xcd_block(int b, int n, int reverse = 0) {
   constexpr int X = 8;
   const int q = n / X, r = n - q * X;
   const int x = b % X, k = b / X;
-  // reverse: the same chunk, last block first.  Consecutive sweeps of a Mult run in opposite directions (operator.hpp):
+  // reverse: the same chunk, last block first.  Consecutive sweeps of a Mult run in opposite directions (launch.hpp):
   // what the previous sweep wrote LAST -- still in this XCD's L2 and in the memory-side cache -- is read FIRST, instead of
   // every sweep streaming 0.6 - 1 GB through a least-recently-used cache in the one order that never hits
   const int kk = reverse ? (q + (x < r ? 1 : 0)) - 1 - k : k;
@@ -3273,96 +3213,6 @@ __global__ __launch_bounds__(256) void k_point_eval(typename PH::KArg prm_k, int
     out[i] = PH::electric_conductivity(prm, u);
   } else {
     out[i] = PH::max_char_speed(prm, u);
-  }
-}
-
-// One block reduces the 50 176 per-block maxima of cfg2: a lane's loads must not wait for each other (round 2: one
-// dependent load per iteration, 196 iterations of a full memory latency = 75 us per call of the time loop's k_step_end)
-template <int BLOCK>
-__device__ inline double strided_max(int n, const double *__restrict__ v) {
-  constexpr int UN = 8;
-  double m[UN];
-#pragma unroll
-  for (int u = 0; u < UN; u++) m[u] = 0.0;
-  int i = threadIdx.x;
-  for (; i + (UN - 1) * BLOCK < n; i += UN * BLOCK) {
-    double t[UN];
-#pragma unroll
-    for (int u = 0; u < UN; u++) t[u] = v[i + u * BLOCK];  // UN independent loads in flight
-#pragma unroll
-    for (int u = 0; u < UN; u++) m[u] = fmax(m[u], t[u]);
-  }
-  for (; i < n; i += BLOCK) m[0] = fmax(m[0], v[i]);
-#pragma unroll
-  for (int u = 1; u < UN; u++) m[0] = fmax(m[0], m[u]);
-  return m[0];
-}
-
-// max over the per-block maxima written by k_flux (one block)
-template <int BLOCK>
-__global__ void k_reduce_max(int n, const double *__restrict__ v, double *__restrict__ out) {
-  __shared__ double s[BLOCK];
-  const double m = strided_max<BLOCK>(n, v);
-  s[threadIdx.x] = m;
-  __syncthreads();
-  for (int off = BLOCK / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off) s[threadIdx.x] = fmax(s[threadIdx.x], s[threadIdx.x + off]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *out = s[0];
-}
-
-// =============================================================================================
-// RK4 stage combinations (MFEM RK4Solver::Step) as one streaming pass per stage:
-//   stage 1: y = x + dt/2 k, z = x + dt/6 k     stage 2: y = x + dt/2 k, z += dt/3 k
-//   stage 3: y = x + dt k,   z += dt/3 k        stage 4: x = z + dt/6 k (+ NaN census, species clamp)
-// =============================================================================================
-template <int BLOCK>
-__global__ void k_rk4_stage(int stage, int64_t n, int64_t ndofs, int sp_first, int sp_last, double dt_host,
-                            const double *__restrict__ dt_dev, double *__restrict__ x, const double *__restrict__ k,
-                            double *__restrict__ y, double *__restrict__ z, unsigned long long *__restrict__ nan_count) {
-  const double dt = dt_dev ? *dt_dev : dt_host;  // tpsrhs_advance keeps dt in device memory
-  unsigned long long bad = 0;
-  for (int64_t i = blockIdx.x * static_cast<int64_t>(BLOCK) + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * BLOCK) {
-    const double ki = k[i];
-    if (stage == 1) {
-      const double xi = x[i];
-      y[i] = xi + (dt / 2) * ki;
-      z[i] = xi + (dt / 6) * ki;
-    } else if (stage == 2) {
-      y[i] = x[i] + (dt / 2) * ki;
-      z[i] += (dt / 3) * ki;
-    } else if (stage == 3) {
-      y[i] = x[i] + dt * ki;
-      z[i] += (dt / 3) * ki;
-    } else {
-      double v = z[i] + (dt / 6) * ki;
-      if (v != v) bad++;
-      const int64_t eq = i / ndofs;
-      if (eq >= sp_first && eq < sp_last) v = fmax(v, 0.0);  // Check_Undershoot
-      x[i] = v;
-    }
-  }
-  if (stage == 4 && bad) atomicAdd(nan_count, bad);
-}
-
-// End of a step of tpsrhs_advance (src/M2ulPhyS.cpp:2004-2016): time += dt; with a variable time step
-// dt = CFL hmin / max_char_speed / dim from the per-block maxima the last k_flux left.  ctl = {dt, time, speed}.
-template <int BLOCK>
-__global__ void k_step_end(int n, const double *__restrict__ block_speed, double *__restrict__ ctl, int constant_dt,
-                           double cfl_hmin_over_dim) {
-  __shared__ double s[BLOCK];
-  const double m = strided_max<BLOCK>(n, block_speed);
-  s[threadIdx.x] = m;
-  __syncthreads();
-  for (int off = BLOCK / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off) s[threadIdx.x] = fmax(s[threadIdx.x], s[threadIdx.x + off]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    ctl[1] += ctl[0];
-    ctl[2] = s[0];
-    if (!constant_dt) ctl[0] = cfl_hmin_over_dim / s[0];
   }
 }
 

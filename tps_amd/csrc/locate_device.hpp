@@ -2,7 +2,7 @@
 // to gslib's FindPointsGSLIB when it carries a field from one mesh to another (utils/pfield_interpolate.cpp:114-142:
 // the physical coordinates of every target node through ElementTransformation::Transform, then finder.Setup on the source
 // mesh and finder.Interpolate; src/cycle_avg_joule_coupling.cpp:159-363 does the same in both directions at every coupling
-// iteration).  Included by tpsrhs.hip only: the kernel families do not see it.  The evaluation half is k_sample
+// iteration).  Included by sampling.hip only: the kernel families do not see it.  The evaluation half is k_sample
 // (sampling.hpp), unchanged.
 //
 // The location rule is point_locate.hpp's locate_one, the text the host locator runs: the point's one bin, its elements in

@@ -4,7 +4,7 @@
 #ifndef TPSRHS_PLASMA_FAMILY_HPP_
 #define TPSRHS_PLASMA_FAMILY_HPP_
 
-#include "operator.hpp"
+#include "launch.hpp"
 #include "physics_plasma.hpp"
 
 template <int DIM, int NVEL, int NSP, bool AMBI, bool TWOT, int TR>

@@ -11,7 +11,7 @@
 #ifndef TPSRHS_PLASMA_VIS_FAMILY_HPP_
 #define TPSRHS_PLASMA_VIS_FAMILY_HPP_
 
-#include "operator.hpp"
+#include "launch.hpp"
 #include "physics_plasma.hpp"
 
 template <int DIM, int NVEL, int NSP, bool AMBI, bool TWOT, int TR>

@@ -14,7 +14,7 @@
 // values, the element with the lower index answers.  That choice is part of the contract (include/tpsrhs.h).
 //
 // Two parts: build_locate_grid makes the search structure (host only), locate_one is the rule for ONE point, and it, with
-// what it calls, is marked TPSRHS_HD -- __host__ __device__ when hipcc compiles tpsrhs.hip, nothing for a plain C++ compiler --
+// what it calls, is marked TPSRHS_HD -- __host__ __device__ when hipcc compiles sampling.hip, nothing for a plain C++ compiler --
 // so that the device locator (locate_device.hpp: k_locate) runs this very text.
 #ifndef TPSRHS_POINT_LOCATE_HPP_
 #define TPSRHS_POINT_LOCATE_HPP_
@@ -26,17 +26,12 @@
 #include <vector>
 
 #include "../../include/tpsrhs.h"
+#include "division_mode.hpp"
 
-// IEEE divisions in the functions that open with this, whatever the including unit has switched on before (tpsrhs.hip
-// includes the plasma point physics first, which replaces x / y by x * (1 / y) from there to the end of the unit): the plane
-// lattice is the reference's bit for bit, and the Newton corrections are what a restatement computes.
-#if defined(__clang__)
-#define TPSRHS_IEEE_DIVISION _Pragma("clang fp reciprocal(off)")
-#else
-#define TPSRHS_IEEE_DIVISION
-#endif
+// IEEE divisions (TPSRHS_IEEE_DIVISION) in the functions of this header that divide: the plane lattice is the reference's
+// bit for bit, and the Newton corrections are what a restatement computes.
 
-// The per-point half (locate_one and what it calls) runs on the host and, in tpsrhs.hip, on the device (locate_device.hpp)
+// The per-point half (locate_one and what it calls) runs on the host and, in sampling.hip, on the device (locate_device.hpp)
 #if defined(__HIPCC__)
 #define TPSRHS_HD __host__ __device__
 #else

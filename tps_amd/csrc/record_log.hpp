@@ -1,4 +1,4 @@
-// The host bookkeeping shared by everything that reads x between two steps of the device time loop (tpsrhs.hip:
+// The host bookkeeping shared by everything that reads x between two steps of the device time loop (time_loop.hip:
 // after_step / work_due_after_next): the statistics, the probe records and the monitor records.  Plain C++17, no HIP:
 // tests/record_log_main.cpp drives it alone.
 //

@@ -1,6 +1,6 @@
 // Values of a byNODES DG field at arbitrary points, and probe records taken inside the device time loop: what the reference
 // does with gslib (FindPointsGSLIB::Interpolate, src/gslib_interpolator.cpp:69-84) for its plane dump
-// (the planeDump block of M2ulPhyS::solveStep, src/M2ulPhyS.cpp:2052-2096).  Included by tpsrhs.hip only: the kernel families do not see it.
+// (the planeDump block of M2ulPhyS::solveStep, src/M2ulPhyS.cpp:2052-2096).  Included by sampling.hip only: the kernel families do not see it.
 // The host half -- which element holds a point, and where in it -- is point_locate.hpp.
 //
 // A field value at a point of element e with reference coordinates xi in [0,1]^dim is
@@ -65,7 +65,7 @@ struct tpsrhs_probe_log {
   DevBuf<double> d_times;   // [capacity], copied from d_ctl[1] on the stream
 };
 
-// behind tpsrhs_operator::sampling; owned by tpsrhs.hip
+// behind tpsrhs_operator::sampling; created by sampling.hip, owned by the operator
 struct tpsrhs_sampling_state {
   std::vector<std::unique_ptr<tpsrhs_sampler>> samplers;
   tpsrhs_probe_log probe;

@@ -1,7 +1,7 @@
 // Running mean of the primitive state and running velocity covariances (the reference's "rms" field): what
 // Averaging::addSample computes once per sampled iteration of the time loop (src/M2ulPhyS.cpp:2099;
 // src/averaging.cpp:198-234 the sampling condition and the counters, :331-435 the update), stored by the reference as
-// /meanSolution and /rmsData.  Included by tpsrhs.hip only: the kernel families do not see it.
+// /meanSolution and /rmsData.  Included by statistics.hip only: the kernel families do not see it.
 //
 // State: mean[neq][ndofs] in the layout of x (byNODES); vari[nvar][ndofs], nvar = nvel (nvel + 1) / 2, the diagonal first,
 // then the pairs i < j in row-major order -- uu vv ww uv uw vw for three velocity components, uu vv uv for two
@@ -11,8 +11,10 @@
 //   mean = (ns_mean * mean + s) / (ns_mean + 1)                          every row
 //   vari = (vari * ns_vari + d_i d_j) / (ns_vari + 1),  d_i = s_i - mean_i  with the UPDATED mean, velocity rows only
 // and both counters go up by one.  This is the reference's recurrence, not the textbook variance: two samples a, b give
-// (b - a)^2 / 8.  Divisions, not reciprocal multiplies, so that a restatement agrees to rounding.  A field whose counter is
-// 0 counts as zero whatever it holds (addSample zeroes it first: 0 * NaN would be NaN).
+// (b - a)^2 / 8.  The quotients are multiplications by the reciprocal of the divisor (TPSRHS_RECIPROCAL_DIVISION in both
+// functions below): what the library has always been compiled to, a rounding away from a restatement that divides
+// (DESIGN.md section 9 keeps the IEEE form as an open decision).  A field whose counter is 0 counts as zero whatever it
+// holds (addSample zeroes it first: 0 * NaN would be NaN).
 //
 // Two deliberate differences from the reference:
 //  (a) The reference samples the grid function Up, which holds the primitives of the input of the step's LAST Mult
@@ -29,9 +31,10 @@
 #include <cstdint>
 
 #include "device_buffer.hpp"
+#include "division_mode.hpp"
 #include "record_log.hpp"
 
-// behind tpsrhs_operator::stats (tpsrhs_stats_configure); owned by tpsrhs.hip
+// behind tpsrhs_operator::stats (tpsrhs_stats_configure); created by statistics.hip, owned by the operator
 struct tpsrhs_stats_state {
   // interval, start: the reference's sampleFreq and startIter; count: the steps taken by tpsrhs_advance /
   // tpsrhs_advance_with (+ tpsrhs_stats_set_iter)
@@ -49,6 +52,7 @@ template <int NVEL, bool VARI>
 __device__ __forceinline__ void stats_node(int neq, int64_t n, double nm, double nv, bool mean_is_zero, bool vari_is_zero,
                                            const double *__restrict__ prim, double sp, double *__restrict__ mean,
                                            double *__restrict__ vari) {
+  TPSRHS_RECIPROCAL_DIVISION
   auto update = [&](int r, double s) {
     const double m = mean_is_zero ? 0.0 : mean[r * n];
     const double mn = (nm * m + s) / (nm + 1.0);
@@ -87,6 +91,7 @@ template <int NVEL, bool VARI, bool VEC, int BLOCK>
 __global__ void __launch_bounds__(BLOCK)
     k_stats_sample(int neq, int64_t n, int ns_mean, int ns_vari, const double *__restrict__ prim, const double *__restrict__ p,
                    double *__restrict__ mean, double *__restrict__ vari) {
+  TPSRHS_RECIPROCAL_DIVISION
   const double nm = static_cast<double>(ns_mean), nv = static_cast<double>(ns_vari);
   const bool mz = ns_mean == 0, vz = ns_vari == 0;
   const int64_t first = blockIdx.x * static_cast<int64_t>(BLOCK) + threadIdx.x, stride = static_cast<int64_t>(gridDim.x) * BLOCK;

@@ -1,12 +1,16 @@
 // The stage combinations of the reference's other explicit integrators (src/M2ulPhyS.cpp:721-739, 2722-2736: MFEM's
 // ForwardEulerSolver, RK2Solver(1.0) and RK3SSPSolver [third party: MFEM >= 4.4, linalg/ode.cpp]) around the plain Mult.
-// Included by tpsrhs.hip only: the kernel families do not see it.
+// With them the kernels of the loop itself: RK4's stage pass (the form without the fusion into k_flux), the end of a step
+// and the reduction of the per-block maximum speeds.  Included by time_loop.hip and, for k_reduce_max, by tpsrhs.hip: the
+// kernel families do not see it.
 #ifndef TPSRHS_TIME_INTEGRATORS_HPP_
 #define TPSRHS_TIME_INTEGRATORS_HPP_
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "division_mode.hpp"
 
 namespace tpsrhs {
 
@@ -31,6 +35,7 @@ struct RkOpTraits {
 
 template <int OP>
 __device__ __forceinline__ void rk_combine(double dt, double &x, double k, double &y) {
+  TPSRHS_RECIPROCAL_DIVISION
   if constexpr (OP == RK_EULER) {
     x = x + dt * k;
   } else if constexpr (OP == RK2_STAGE1) {
@@ -98,6 +103,98 @@ __global__ void __launch_bounds__(BLOCK)
   }
   if constexpr (T::last) {
     if (bad) atomicAdd(nan_count, bad);
+  }
+}
+
+// One block reduces the 50 176 per-block maxima of cfg2: a lane's loads must not wait for each other (round 2: one
+// dependent load per iteration, 196 iterations of a full memory latency = 75 us per call of the time loop's k_step_end)
+template <int BLOCK>
+__device__ inline double strided_max(int n, const double *__restrict__ v) {
+  constexpr int UN = 8;
+  double m[UN];
+#pragma unroll
+  for (int u = 0; u < UN; u++) m[u] = 0.0;
+  int i = threadIdx.x;
+  for (; i + (UN - 1) * BLOCK < n; i += UN * BLOCK) {
+    double t[UN];
+#pragma unroll
+    for (int u = 0; u < UN; u++) t[u] = v[i + u * BLOCK];  // UN independent loads in flight
+#pragma unroll
+    for (int u = 0; u < UN; u++) m[u] = fmax(m[u], t[u]);
+  }
+  for (; i < n; i += BLOCK) m[0] = fmax(m[0], v[i]);
+#pragma unroll
+  for (int u = 1; u < UN; u++) m[0] = fmax(m[0], m[u]);
+  return m[0];
+}
+
+// max over the per-block maxima written by k_flux (one block)
+template <int BLOCK>
+__global__ void k_reduce_max(int n, const double *__restrict__ v, double *__restrict__ out) {
+  __shared__ double s[BLOCK];
+  const double m = strided_max<BLOCK>(n, v);
+  s[threadIdx.x] = m;
+  __syncthreads();
+  for (int off = BLOCK / 2; off > 0; off >>= 1) {
+    if (threadIdx.x < off) s[threadIdx.x] = fmax(s[threadIdx.x], s[threadIdx.x + off]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *out = s[0];
+}
+
+// =============================================================================================
+// RK4 stage combinations (MFEM RK4Solver::Step) as one streaming pass per stage:
+//   stage 1: y = x + dt/2 k, z = x + dt/6 k     stage 2: y = x + dt/2 k, z += dt/3 k
+//   stage 3: y = x + dt k,   z += dt/3 k        stage 4: x = z + dt/6 k (+ NaN census, species clamp)
+// =============================================================================================
+template <int BLOCK>
+__global__ void k_rk4_stage(int stage, int64_t n, int64_t ndofs, int sp_first, int sp_last, double dt_host,
+                            const double *__restrict__ dt_dev, double *__restrict__ x, const double *__restrict__ k,
+                            double *__restrict__ y, double *__restrict__ z, unsigned long long *__restrict__ nan_count) {
+  TPSRHS_IEEE_DIVISION
+  const double dt = dt_dev ? *dt_dev : dt_host;  // tpsrhs_advance keeps dt in device memory
+  unsigned long long bad = 0;
+  for (int64_t i = blockIdx.x * static_cast<int64_t>(BLOCK) + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * BLOCK) {
+    const double ki = k[i];
+    if (stage == 1) {
+      const double xi = x[i];
+      y[i] = xi + (dt / 2) * ki;
+      z[i] = xi + (dt / 6) * ki;
+    } else if (stage == 2) {
+      y[i] = x[i] + (dt / 2) * ki;
+      z[i] += (dt / 3) * ki;
+    } else if (stage == 3) {
+      y[i] = x[i] + dt * ki;
+      z[i] += (dt / 3) * ki;
+    } else {
+      double v = z[i] + (dt / 6) * ki;
+      if (v != v) bad++;
+      const int64_t eq = i / ndofs;
+      if (eq >= sp_first && eq < sp_last) v = fmax(v, 0.0);  // Check_Undershoot
+      x[i] = v;
+    }
+  }
+  if (stage == 4 && bad) atomicAdd(nan_count, bad);
+}
+
+// End of a step of tpsrhs_advance (src/M2ulPhyS.cpp:2004-2016): time += dt; with a variable time step
+// dt = CFL hmin / max_char_speed / dim from the per-block maxima the last k_flux left.  ctl = {dt, time, speed}.
+template <int BLOCK>
+__global__ void k_step_end(int n, const double *__restrict__ block_speed, double *__restrict__ ctl, int constant_dt,
+                           double cfl_hmin_over_dim) {
+  TPSRHS_IEEE_DIVISION
+  __shared__ double s[BLOCK];
+  const double m = strided_max<BLOCK>(n, block_speed);
+  s[threadIdx.x] = m;
+  __syncthreads();
+  for (int off = BLOCK / 2; off > 0; off >>= 1) {
+    if (threadIdx.x < off) s[threadIdx.x] = fmax(s[threadIdx.x], s[threadIdx.x + off]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    ctl[1] += ctl[0];
+    ctl[2] = s[0];
+    if (!constant_dt) ctl[0] = cfl_hmin_over_dim / s[0];
   }
 }
 

@@ -1,24 +1,22 @@
 // libtpsrhs.so -- implementation of include/tpsrhs.h for gfx950 (MI355X).
 //
 // Host side: builds the face topology and the 1-D operator tables, keeps every field resident in
-// HBM, and enqueues the three sweeps of kernels.hpp on one HIP stream per operator.  There is no
+// HBM, and enqueues the three sweeps of kernels.hpp on one HIP stream per operator (launch.hpp).  There is no
 // CPU fallback: without a HIP device tpsrhs_create returns TPSRHS_ERR_NO_DEVICE.
-#include "operator.hpp"
+//
+// This unit: the family loader, the parameter blocks and setup, create / destroy / mult, the setters and getters, timing,
+// statuses, the two visualization entries, and the planar dry-air instantiations of the sweeps.  The other features of
+// the C ABI have units of their own -- time_loop.hip, statistics.hip, sampling.hip, integrals.hip, wall_distance.hip,
+// probes.hip -- and share abi_support.hpp with this one.
+#include "abi_support.hpp"
 #include "element_geometry.hpp"
-#include "integrals.hpp"
-#include "locate_device.hpp"
+#include "launch.hpp"
 #include "operator_plan.hpp"
 #include "physics_dryair.hpp"
 #include "physics_dryair_axisym.hpp"
 #include "physics_plasma.hpp"
 #include "plasma_params_host.hpp"
-#include "point_locate.hpp"
-#include "record_log.hpp"
-#include "sampling.hpp"
-#include "statistics.hpp"
-#include "time_integrators.hpp"
-#include "wall_distance.hpp"
-#include "wall_faces.hpp"
+#include "time_integrators.hpp"  // k_reduce_max
 
 #include <dlfcn.h>
 
@@ -35,7 +33,25 @@ void pick_dryair_axisym(tpsrhs_operator *op);
 void pick_lte_axisym(tpsrhs_operator *op);
 void pick_dryair_les(tpsrhs_operator *op);
 
-static thread_local std::string g_last_error;
+TableDev upload_table(std::vector<DevBuf<void>> &owner, const tpsrhs_table &t) {
+  std::vector<double> buf;
+  TableDev td = table_coeffs(t, buf);
+  owner.emplace_back(DevBuf<double>(buf));
+  double *d = static_cast<double *>(owner.back().get());
+  td.x = d;
+  td.a = d + td.n;
+  td.b = d + 2 * td.n;
+  return td;
+}
+
+const std::vector<double> &coulomb_table_host() {
+  static const std::vector<double> table = [] {
+    std::vector<double> t(coulomb::SIZE);
+    coll::coulomb_table_fill(t.data());
+    return t;
+  }();
+  return table;
+}
 
 namespace {
 
@@ -93,28 +109,6 @@ family_pick_fn load_family(const std::string &unit) {
   throw Unsupported("kernel family " + unit + " is not available (run __graft_entry__.build()):" + tried);
 }
 
-// LinearTable::LinearTable (src/table.cpp:39-50): interval coefficients (plasma_params_host.hpp), uploaded with the abscissae
-TableDev upload_table(tpsrhs_operator *op, const tpsrhs_table &t) {
-  std::vector<double> buf;
-  TableDev td = table_coeffs(t, buf);
-  op->d_extra.emplace_back(DevBuf<double>(buf));
-  double *d = static_cast<double *>(op->d_extra.back().get());
-  td.x = d;
-  td.a = d + td.n;
-  td.b = d + 2 * td.n;
-  return td;
-}
-
-// the polynomial table of the Coulomb fits (coulomb_table.hpp), filled once per process from the literals of the closure
-const std::vector<double> &coulomb_table_host() {
-  static const std::vector<double> table = [] {
-    std::vector<double> t(coulomb::SIZE);
-    coll::coulomb_table_fill(t.data());
-    return t;
-  }();
-  return table;
-}
-
 // the parameter block of the plasma kernels (plasma_params_host.hpp) into the operator, the chemistry block to the device
 template <int NSP>
 void fill_plasma_params(tpsrhs_operator *op, const tpsrhs_disc *disc, const tpsrhs_physics *phys, int num_bcs,
@@ -123,7 +117,7 @@ void fill_plasma_params(tpsrhs_operator *op, const tpsrhs_disc *disc, const tpsr
   PlasmaParams<NSP> &p = *new (op->params) PlasmaParams<NSP>;
   std::unique_ptr<ChemDev> c(new ChemDev);
   try {
-    tpsrhs::fill_plasma_params<NSP>(p, *c, disc, phys, num_bcs, bcs, [op](const tpsrhs_table &t) { return upload_table(op, t); });
+    tpsrhs::fill_plasma_params<NSP>(p, *c, disc, phys, num_bcs, bcs, [op](const tpsrhs_table &t) { return upload_table(op->d_extra, t); });
   } catch (const UnsupportedConfig &e) {  // (its header is also built alone, on the host, by tests/host_physics: it keeps its own type)
     throw Unsupported(e.what());
   }
@@ -165,13 +159,13 @@ void fill_mixture_params(tpsrhs_operator *op, const OperatorPlan &pl, const tpsr
 // the tables of the table gas (the plan has checked their scales and that e(T) increases)
 void upload_lte_tables(tpsrhs_operator *op, LteParams *lp, const tpsrhs_physics *phys) {
   const tpsrhs_lte &in = phys->lte;
-  lp->tab_e = upload_table(op, in.energy_table);
-  lp->tab_R = upload_table(op, in.gas_constant_table);
-  lp->tab_c = upload_table(op, in.sound_speed_table);
+  lp->tab_e = upload_table(op->d_extra, in.energy_table);
+  lp->tab_R = upload_table(op->d_extra, in.gas_constant_table);
+  lp->tab_c = upload_table(op->d_extra, in.sound_speed_table);
   tpsrhs_table rev = in.energy_table;  // "Construct e -> T table from T -> e", src/M2ulPhyS.cpp:193-200
   rev.x_data = in.energy_table.f_data;
   rev.f_data = in.energy_table.x_data;
-  lp->tab_T = upload_table(op, rev);
+  lp->tab_T = upload_table(op->d_extra, rev);
   {  // search aid of the inverse table: the interval of the left edge of uniform bins over the energy axis
     const int N = in.energy_table.n_data, nh = 4 * (N - 1);
     const double *ex = in.energy_table.f_data;
@@ -197,11 +191,11 @@ void upload_lte_tables(tpsrhs_operator *op, LteParams *lp, const tpsrhs_physics 
   };
   lp->thermo_same_grid = same_grid(in.energy_table, in.gas_constant_table) && same_grid(in.energy_table, in.sound_speed_table);
   lp->trans_same_grid = same_grid(in.viscosity_table, in.conductivity_table);
-  lp->tab_mu = upload_table(op, in.viscosity_table);
-  lp->tab_k = upload_table(op, in.conductivity_table);
-  lp->tab_sigma = upload_table(op, in.electric_conductivity_table);
+  lp->tab_mu = upload_table(op->d_extra, in.viscosity_table);
+  lp->tab_k = upload_table(op->d_extra, in.conductivity_table);
+  lp->tab_sigma = upload_table(op->d_extra, in.electric_conductivity_table);
   lp->radiation = phys->radiation.model;
-  if (lp->radiation == TPSRHS_NET_EMISSION) lp->tab_nec = upload_table(op, phys->radiation.nec_table);
+  if (lp->radiation == TPSRHS_NET_EMISSION) lp->tab_nec = upload_table(op->d_extra, phys->radiation.nec_table);
 }
 
 // Fluxes: sub-grid scale model and viscous sponge (src/fluxes.cpp:223-246) -> the LES flavour of the dry-air kernels
@@ -294,7 +288,7 @@ void build_nr_tables(tpsrhs_operator *op, const tpsrhs_bc *bcs) {
     }
   }
   if (tp.num_shared > 0 && !op->reduce)
-    throw std::runtime_error("halo: a partitioned mesh with non-reflecting patches needs runtime.reduce");
+    throw HaloError("halo: a partitioned mesh with non-reflecting patches needs runtime.reduce");
   op->n_nr_faces = static_cast<int>(nrf.size());
   op->d_bc_sums = DevBuf<double>(MAXBC * (TPSRHS_MAXEQUATIONS + 1));
   HIP_CHECK(hipMemset(op->d_bc_sums.get(), 0, MAXBC * (TPSRHS_MAXEQUATIONS + 1) * sizeof(double)));
@@ -362,13 +356,7 @@ void setup(tpsrhs_operator *op, const tpsrhs_mesh *mesh, const tpsrhs_disc *disc
   op->neq = pl.neq;
   op->phys = *phys;
 
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    struct NoDevice : std::runtime_error {
-      NoDevice() : std::runtime_error("no HIP device visible; tpsrhs has no CPU path") {}
-    };
-    throw NoDevice();
-  }
+  require_device("no HIP device visible; tpsrhs has no CPU path");
   op->device = rt ? rt->device : 0;
   HIP_CHECK(hipSetDevice(op->device));
   op->stream = rt ? static_cast<hipStream_t>(rt->stream) : nullptr;
@@ -424,75 +412,6 @@ void setup(tpsrhs_operator *op, const tpsrhs_mesh *mesh, const tpsrhs_disc *disc
     for (auto &e : set) HIP_CHECK(hipEventCreate(&e));
 }
 
-int fail(int code, const std::string &msg) {
-  g_last_error = msg;
-  return code;
-}
-
-template <class F>
-int guarded(F &&f) {
-  try {
-    f();
-    return TPSRHS_OK;
-  } catch (const Unsupported &e) {
-    return fail(TPSRHS_ERR_UNSUPPORTED, e.what());
-  } catch (const DeviceError &e) {
-    return fail(TPSRHS_ERR_DEVICE, e.what());
-  } catch (const std::invalid_argument &e) {
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, e.what());
-  } catch (const std::runtime_error &e) {
-    const std::string w = e.what();
-    if (w.find("no HIP device") != std::string::npos) return fail(TPSRHS_ERR_NO_DEVICE, w);
-    if (w.find("halo") != std::string::npos) return fail(TPSRHS_ERR_HALO, w);
-    return fail(TPSRHS_ERR_MESH, w);
-  } catch (const std::exception &e) {
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, e.what());
-  }
-}
-
-// Running statistics (statistics.hpp): at the end of this file
-void stats_release(tpsrhs_operator *h);
-void stats_sample(tpsrhs_operator *h, const double *x);
-// Probe records (sampling.hpp): at the end of this file
-void sampling_release(tpsrhs_operator *h);
-void transfer_release(tpsrhs_operator *h);
-void probe_record(tpsrhs_operator *h, const double *x);
-// Monitor records (integrals.hpp): at the end of this file
-void integrals_release(tpsrhs_operator *h);
-void monitor_record(tpsrhs_operator *h, const double *x);
-// What the time loop does between two steps, and whether any of it falls after the first of the next two: everything that
-// reads x between steps goes through these two, so that the loop itself knows nothing about statistics, probes or the
-// monitor.  Each observer has one StepCadence (record_log.hpp; interval 0: off), which answers both questions.
-inline void after_step(tpsrhs_operator *h, const double *x) {
-  if (h->stats && h->stats->cadence.tick()) stats_sample(h, x);
-  if (h->sampling && h->sampling->probe.cadence.tick()) probe_record(h, x);
-  if (h->integrals && h->integrals->monitor.cadence.tick()) monitor_record(h, x);
-}
-inline bool work_due_after_next(const tpsrhs_operator *h) {
-  return (h->stats && h->stats->cadence.due_after_next()) || (h->sampling && h->sampling->probe.cadence.due_after_next()) ||
-         (h->integrals && h->integrals->monitor.cadence.due_after_next());
-}
-
-// f(std::integral_constant<int, DIM>, std::integral_constant<int, P>) for the operator's dim and order: the (dim, order) pairs
-// the post-processing kernels of this unit are built for, listed once
-template <int N>
-using int_c = std::integral_constant<int, N>;
-template <class F>
-void with_dim_order(const tpsrhs_operator *h, const char *who, F &&f) {
-  switch (h->dim * 10 + h->order) {
-    case 21: f(int_c<2>(), int_c<1>()); break;
-    case 22: f(int_c<2>(), int_c<2>()); break;
-    case 23: f(int_c<2>(), int_c<3>()); break;
-    case 24: f(int_c<2>(), int_c<4>()); break;
-    case 25: f(int_c<2>(), int_c<5>()); break;
-    case 31: f(int_c<3>(), int_c<1>()); break;
-    case 32: f(int_c<3>(), int_c<2>()); break;
-    case 33: f(int_c<3>(), int_c<3>()); break;
-    case 34: f(int_c<3>(), int_c<4>()); break;
-    case 35: f(int_c<3>(), int_c<5>()); break;
-    default: throw Unsupported(std::string(who) + ": dim 2 or 3 and polynomial orders 1..5 are built");
-  }
-}
 
 }  // namespace
 
@@ -520,10 +439,9 @@ int tpsrhs_create(const tpsrhs_mesh *mesh, const tpsrhs_disc *disc, const tpsrhs
 
 int tpsrhs_destroy(tpsrhs_handle h) {
   if (!h) return TPSRHS_OK;
-  stats_release(h);
-  transfer_release(h);
-  sampling_release(h);
-  integrals_release(h);
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);  // a sample, a record or a reduction may still be running
+  transfer_forget(h);
   delete h;
   return TPSRHS_OK;
 }
@@ -561,254 +479,6 @@ int tpsrhs_mult_host(tpsrhs_handle h, const double *x, double *y, double time, d
     HIP_CHECK(hipStreamSynchronize(h->stream));
   });
 }
-
-// ---- the device time loop ------------------------------------------------------------------------------------------------
-// Its state is tpsrhs_operator::loop; the rules are in trace_chain.hpp.  The functions stay in this order, and rk_stages
-// after every other launch of this unit: the compiler numbers a unit's kernels by their first launch in the source, and
-// tools/device_asm_diff.py compares the local labels that carry that number.
-namespace {
-// The stage vectors in loop.d_rk (3 n doubles, with loop.d_nan allocated at the first step): k | y | z, or k | y with y on
-// an even offset, so that an odd n keeps the 16-byte accesses (y then ends at or before 2 n + 1 <= 3 n).
-struct StageScratch {
-  double *k, *y, *z;
-};
-StageScratch stage_scratch(tpsrhs_operator *h, int64_t n, bool even_offsets) {
-  tpsrhs_operator::TimeLoop &lp = h->loop;
-  if (!lp.d_rk) {
-    lp.d_rk = DevBuf<double>(3 * n);
-    lp.d_nan = DevBuf<unsigned long long>(1);
-    HIP_CHECK(hipMemsetAsync(lp.d_nan.get(), 0, sizeof(unsigned long long), h->stream));
-  }
-  double *k = lp.d_rk.get();
-  if (even_offsets) return {k, k + ((n + 1) & ~static_cast<int64_t>(1)), nullptr};
-  return {k, k + n, k + 2 * n};
-}
-// {dt, time, max speed} of the loop in device memory; the probe and monitor records copy the time from there
-double *loop_ctl(tpsrhs_operator *h) {
-  if (!h->loop.d_ctl) h->loop.d_ctl = DevBuf<double>(3);
-  return h->loop.d_ctl.get();
-}
-
-// the four stages of MFEM's RK4Solver::Step around Mult; dt by value or from device memory (dt_dev)
-void rk4_stages(tpsrhs_operator *h, double *x, double dt, const double *dt_dev) {
-  const int64_t n = static_cast<int64_t>(h->neq) * h->ndofs;
-  const StageScratch sc = stage_scratch(h, n, false);
-  double *k = sc.k, *y = sc.y, *z = sc.z;
-  TraceChain &chain = h->loop.chain;
-  chain.begin_step();
-  ScopeExit step([&](bool) { chain.end_step(); });
-  const int sp_first = h->loop.sp_first, sp_last = h->loop.sp_last;
-  const int grid = static_cast<int>(std::min<int64_t>((n + 255) / 256, 8192));
-  if (!h->forcing_active) {
-    // The stage combinations in k_flux's epilogue (RkDev, kernels.hpp): k never goes to memory, the accumulator of
-    // RK4Solver::Step is recovered from the stage states at the end.  (The optional forcing terms add to the residual in
-    // a pass of their own after k_flux: with them the separate stage kernel below stays.)
-    double *y2 = k, *y3 = y, *y4 = z;  // the three stage states
-    const double *ins[4] = {x, y2, y3, y4};
-    double *outs[4] = {y2, y3, y4, x};
-    for (int stage = 1; stage <= 4; stage++) {
-      RkDev r = {};
-      r.mode = stage;
-      r.sp_first = sp_first;
-      r.sp_last = sp_last;
-      r.dt_host = dt;
-      r.dt_dev = dt_dev;
-      r.x0 = x;
-      r.y2 = y2;
-      r.y3 = y3;
-      r.y4 = y4;
-      r.out = outs[stage - 1];
-      r.nan_count = h->loop.d_nan.get();
-      h->rk = r;  // in force for this launch only
-      ScopeExit launched([&](bool failed) {
-        h->rk = RkDev{};
-        if (failed) chain.abandon();
-      });
-      h->launch(h, ins[stage - 1], outs[stage - 1], false);
-    }
-    return;
-  }
-  const double *in = x;
-  for (int stage = 1; stage <= 4; stage++) {
-    h->launch(h, in, k, false);  // k_s = f(stage input); SetTime is a no-op for this operator
-    hipLaunchKernelGGL(k_rk4_stage<256>, dim3(grid), dim3(256), 0, h->stream, stage, n, h->ndofs, sp_first, sp_last, dt,
-                       dt_dev, x, k, y, z, h->loop.d_nan.get());
-    HIP_CHECK(hipGetLastError());
-    in = y;
-  }
-}
-
-// Forward Euler, RK2(a = 1) and RK3-SSP: at the end of this file
-void rk_stages(tpsrhs_operator *h, int integrator, double *x, double dt, const double *dt_dev);
-
-// TPSRHS_OK for the integrators that are built; the status of the others, before any device work
-int check_integrator(int integrator, const char *who) {
-  switch (integrator) {
-    case TPSRHS_FORWARD_EULER:
-    case TPSRHS_RK2:
-    case TPSRHS_RK3_SSP:
-    case TPSRHS_RK4: return TPSRHS_OK;
-    case TPSRHS_RK6:
-      return fail(TPSRHS_ERR_UNSUPPORTED, std::string(who) + ": the RK6 integrator (MFEM's eight-stage Verner scheme) is not built; "
-                                              "forwardEuler, rk2, rk3 and rk4 are");
-    default:
-      return fail(TPSRHS_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown integrator " + std::to_string(integrator) +
-                                                   " (the reference's timeIntegratorType: 1, 2, 3, 4 or 6)");
-  }
-}
-
-void step_stages(tpsrhs_operator *h, int integrator, double *x, double dt, const double *dt_dev) {
-  if (integrator == TPSRHS_RK4)
-    rk4_stages(h, x, dt, dt_dev);
-  else
-    rk_stages(h, integrator, x, dt, dt_dev);
-}
-
-int step_with(tpsrhs_handle h, int integrator, const char *who, double *x, double *time, double dt, double *max_char_speed,
-              int64_t *nan_count);
-int advance_with(tpsrhs_handle h, int integrator, const char *who, double *x, double *time, double *dt, int num_steps,
-                 int constant_dt, double cfl, double hmin, int64_t *nan_count);
-}  // namespace
-
-int tpsrhs_rk4_step(tpsrhs_handle h, double *x, double *time, double dt, double *max_char_speed, int64_t *nan_count) {
-  return step_with(h, TPSRHS_RK4, "tpsrhs_rk4_step", x, time, dt, max_char_speed, nan_count);
-}
-
-int tpsrhs_step(tpsrhs_handle h, int integrator, double *x, double *time, double dt, double *max_char_speed,
-                int64_t *nan_count) {
-  return step_with(h, integrator, "tpsrhs_step", x, time, dt, max_char_speed, nan_count);
-}
-
-int tpsrhs_advance(tpsrhs_handle h, double *x, double *time, double *dt, int num_steps, int constant_dt, double cfl,
-                   double hmin, int64_t *nan_count) {
-  return advance_with(h, TPSRHS_RK4, "tpsrhs_advance", x, time, dt, num_steps, constant_dt, cfl, hmin, nan_count);
-}
-
-int tpsrhs_advance_with(tpsrhs_handle h, int integrator, double *x, double *time, double *dt, int num_steps,
-                        int constant_dt, double cfl, double hmin, int64_t *nan_count) {
-  return advance_with(h, integrator, "tpsrhs_advance_with", x, time, dt, num_steps, constant_dt, cfl, hmin, nan_count);
-}
-
-}  // extern "C"
-
-namespace {
-int step_with(tpsrhs_handle h, int integrator, const char *who, double *x, double *time, double dt, double *max_char_speed,
-              int64_t *nan_count) {
-  if (!h || !x || !time) return fail(TPSRHS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
-  if (const int st = check_integrator(integrator, who)) return st;
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(h->device));
-    h->nr_dt = dt;  // the boundary conditions see M2ulPhyS::dt (src/BoundaryCondition.hpp:54)
-    if (h->loop.d_nan) HIP_CHECK(hipMemsetAsync(h->loop.d_nan.get(), 0, sizeof(unsigned long long), h->stream));
-    step_stages(h, integrator, x, dt, nullptr);
-    *time += dt;
-    if (max_char_speed || nan_count) {
-      hipLaunchKernelGGL(k_reduce_max<1024>, dim3(1), dim3(1024), 0, h->stream, h->flux_grid, h->d_block_speed.get(), h->d_speed.get());
-      HIP_CHECK(hipGetLastError());
-      double speed = 0.0;
-      unsigned long long bad = 0;
-      HIP_CHECK(hipMemcpyAsync(&speed, h->d_speed.get(), sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      HIP_CHECK(hipMemcpyAsync(&bad, h->loop.d_nan.get(), sizeof(bad), hipMemcpyDeviceToHost, h->stream));
-      HIP_CHECK(hipStreamSynchronize(h->stream));
-      if (max_char_speed) *max_char_speed = speed;
-      if (nan_count) *nan_count = static_cast<int64_t>(bad);
-    }
-  });
-}
-
-// The stage sequence (step_stages) is all that depends on the integrator: the end of the step, the MIN reduce, the graph,
-// the error paths and the read-back are shared.
-int advance_with(tpsrhs_handle h, int integrator, const char *who, double *x, double *time, double *dt, int num_steps,
-                 int constant_dt, double cfl, double hmin, int64_t *nan_count) {
-  if (!h || !x || !time || !dt) return fail(TPSRHS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
-  if (const int st = check_integrator(integrator, who)) return st;
-  if (num_steps < 0 || !(*dt > 0.0) || (!constant_dt && !(cfl > 0.0 && hmin > 0.0)))
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, std::string(who) + ": needs num_steps >= 0, dt > 0 and (constant dt or cfl, hmin > 0)");
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(h->device));
-    if (!constant_dt && h->topo.num_shared > 0 && !h->reduce)
-      throw std::runtime_error("halo: a variable time step on a partitioned mesh needs runtime.reduce");
-    double *const d_ctl = loop_ctl(h);
-    const double ctl0[3] = {*dt, *time, 0.0};
-    HIP_CHECK(hipMemcpyAsync(d_ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));  // ctl0 lives on this stack frame
-    if (h->loop.d_nan) HIP_CHECK(hipMemsetAsync(h->loop.d_nan.get(), 0, sizeof(unsigned long long), h->stream));
-    const double coef = cfl * hmin / static_cast<double>(h->dim);
-    auto one_step = [&] {
-      step_stages(h, integrator, x, 0.0, d_ctl);
-      hipLaunchKernelGGL(k_step_end<1024>, dim3(1), dim3(1024), 0, h->stream, h->flux_grid, h->d_block_speed.get(), d_ctl,
-                         constant_dt ? 1 : 0, coef);
-      HIP_CHECK(hipGetLastError());
-      if (!constant_dt && h->reduce && h->topo.num_shared > 0) {  // MPI_Allreduce(MIN) of src/M2ulPhyS.cpp:2015
-        if (h->reduce(h->reduce_ctx, d_ctl, 1, TPSRHS_REDUCE_MIN, h->stream) != 0)
-          throw std::runtime_error("halo: reduce callback failed");
-      }
-    };
-    // On one rank a step is a fixed sequence of launches (~17 for RK4) whose arguments do not change from step to step (dt
-    // and the time are in device memory; the two boundary-state buffers swap four times per step): captured once
-    // into a hipGraph and replayed -- the launch overhead matters on small meshes.  Needs a capturable stream (not
-    // the NULL stream), no host callbacks in the step (partitioned meshes keep the plain loop), no timing events.
-    const char *genv = std::getenv("TPSRHS_GRAPH");
-    const bool use_graph = h->stream != nullptr && h->topo.num_shared == 0 && !h->timing && num_steps >= 3 &&
-                           !(genv && genv[0] == '0');
-    const int per_graph = steps_per_graph(integrator, h->n_nr_faces > 0);
-    {
-      // the session: the boundary conditions read dt from device memory, the steps are chained; put back however it ends
-      h->nr_dt_dev = d_ctl;
-      h->loop.chain.begin_advance(integrator == TPSRHS_RK4 && !h->forcing_active);
-      ScopeExit session([&](bool) {
-        h->nr_dt_dev = nullptr;
-        h->loop.chain.end_advance();
-      });
-      // Running statistics and probe records: the host issues every step anyway and knows the iteration number, so it
-      // enqueues the sample or the record between two steps -- never inside the captured graph, whose key knows about neither.
-      int step = 0;
-      if (use_graph) {
-        one_step();  // first step outside the graph: allocations, initial boundary state, its own k_traces sweep
-        after_step(h, x);
-        step = 1;
-        StepKey key;
-        key.x = x;
-        key.constant_dt = constant_dt ? 1 : 0;
-        key.bstate_cur = h->bstate_cur;
-        key.epoch = h->loop.config_epoch;
-        key.integrator = integrator;
-        key.coef = coef;
-        h->loop.graph.ensure(key, h->stream, [&] {
-          for (int i = 0; i < per_graph; i++) one_step();
-        });
-        for (; step + per_graph <= num_steps; step += per_graph) {
-          // a sample or a record between the two steps of one graph: the pair runs as two plain steps (bit-equal to the
-          // replay, as the odd remainder below is), which leave the boundary-state buffers as the graph does
-          const bool split = per_graph == 2 && work_due_after_next(h);
-          for (int i = 0; i < per_graph; i++) {
-            if (split)
-              one_step();
-            else if (i == 0)
-              h->loop.graph.launch(h->stream);
-            after_step(h, x);
-          }
-        }
-      }
-      for (; step < num_steps; step++) {
-        one_step();
-        after_step(h, x);
-      }
-    }
-    double ctl[3] = {0, 0, 0};
-    unsigned long long bad = 0;
-    HIP_CHECK(hipMemcpyAsync(ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, h->stream));
-    if (h->loop.d_nan) HIP_CHECK(hipMemcpyAsync(&bad, h->loop.d_nan.get(), sizeof(bad), hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    *dt = ctl[0];
-    *time = ctl[1];
-    h->nr_dt = ctl[0];
-    if (nan_count) *nan_count = static_cast<int64_t>(bad);
-  });
-}
-}  // namespace
-
-extern "C" {
 
 int tpsrhs_set_dt(tpsrhs_handle h, double dt) {
   if (!h) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_set_dt: NULL handle");
@@ -1061,104 +731,6 @@ int tpsrhs_eval_pointwise(tpsrhs_handle h, int quantity, int64_t n, const double
   });
 }
 
-namespace {
-__global__ void k_table_eval(TableDev t, int64_t n, const double *__restrict__ x, double *__restrict__ f) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (i < n) f[i] = table_eval(t, x[i]);
-}
-}  // namespace
-
-namespace {
-__global__ void k_math_eval(int fn, int64_t n, const double *__restrict__ x, double *__restrict__ y) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (i >= n) return;
-  const double v = x[i];
-  double r;
-  switch (fn) {
-    case 0: r = fexp(v); break;
-    case 1: r = fexp<false>(v); break;
-    case 2: r = flog(v); break;
-    case 3: r = flog_pos(v); break;
-    case 4: r = fast_rcp(v); break;
-    case 5: r = fast_sqrt(v); break;
-    default: r = fast_rsqrt(v); break;
-  }
-  y[i] = r;
-}
-}  // namespace
-
-int tpsrhs_math_eval(int function, int64_t n, const double *x, double *y) {
-  if (function < 0 || function > 6 || n < 0 || !x || !y) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "math_eval");
-  return guarded([&] {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device visible");
-    if (n > 0) {
-      hipLaunchKernelGGL(k_math_eval, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, nullptr, function, n, x, y);
-      HIP_CHECK(hipGetLastError());
-    }
-    HIP_CHECK(hipDeviceSynchronize());
-  });
-}
-
-namespace {
-// route 0: cfit_n; 1: the table with two wave-uniform rounds, then lane by lane; 2: lane by lane only.  1 / Tp^2 = 1.
-__global__ void k_coulomb_eval(int route, const double *tab, int64_t n, const double *__restrict__ x, double *__restrict__ out) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (i >= n) return;
-  coll::Arg a;
-  a.ln = x[i];
-  a.inv2 = 1.0;
-  double g[8];
-  if (route == 0 || !coulomb::in_range(a.ln)) {
-    coll::cfit_tab<8>(nullptr, a, g);
-  } else if (route == 1) {
-    coll::ctab_eval<8, 2>(tab, a.ln, true, g);
-  } else {
-    coll::ctab_eval<8, 0>(tab, a.ln, true, g);
-  }
-#pragma unroll
-  for (int f = 0; f < 8; f++) out[f * n + i] = g[f];
-}
-}  // namespace
-
-// route 3, the LDS window of a wave: coulomb_probe.hip (a unit of its own -- a kernel added to this one renumbers the labels of
-// every kernel the compiler emits after it, and the device code of this unit is compared from commit to commit)
-// (C++ linkage: this declaration stands inside an extern "C" block)
-extern "C++" void coulomb_probe_window(const double *tab, int64_t n, const double *x, double *out);
-
-int tpsrhs_coulomb_eval(int route, int64_t n, const double *x, double *out) {
-  if (route < 0 || route > 3 || n < 0 || !x || !out) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "coulomb_eval");
-  return guarded([&] {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device visible");
-    DevBuf<double> tab(coulomb_table_host());  // its own table, from the same fill as an operator's
-    if (n > 0 && route == 3) {
-      coulomb_probe_window(tab.get(), n, x, out);
-      HIP_CHECK(hipGetLastError());
-    } else if (n > 0) {
-      hipLaunchKernelGGL(k_coulomb_eval, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, nullptr, route, tab.get(), n, x, out);
-      HIP_CHECK(hipGetLastError());
-    }
-    HIP_CHECK(hipDeviceSynchronize());
-  });
-}
-
-int tpsrhs_table_eval(const tpsrhs_table *table, int64_t n, const double *x, double *f) {
-  if (!table || n < 0 || !x || !f) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "table_eval");
-  return guarded([&] {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device visible");
-    tpsrhs_operator tmp;  // owns the device copy of the table for the duration of the call
-    (void)hipGetDevice(&tmp.device);
-    const TableDev td = upload_table(&tmp, *table);
-    if (n > 0) {
-      hipLaunchKernelGGL(k_table_eval, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, nullptr, td, n, x, f);
-      HIP_CHECK(hipGetLastError());
-    }
-    HIP_CHECK(hipDeviceSynchronize());
-  });
-}
-
 int tpsrhs_mult_times(tpsrhs_handle h, int capacity, double *milliseconds) {
   if (!h || h->sets_recorded == 0 || !milliseconds) return 0;
   if (hipStreamSynchronize(h->stream) != hipSuccess) return 0;
@@ -1215,7 +787,7 @@ const char *tpsrhs_status_string(int status) {
     default: return "TPSRHS_ERR_UNKNOWN";
   }
 }
-const char *tpsrhs_last_error(void) { return g_last_error.c_str(); }
+const char *tpsrhs_last_error(void) { return last_error().c_str(); }
 int tpsrhs_get_plasma_conductivity(tpsrhs_handle h, const double *x, double *sigma_out) {
   if (!h || !x || !sigma_out) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_get_plasma_conductivity: NULL argument");
   return guarded([&] {
@@ -1229,870 +801,6 @@ int tpsrhs_get_plasma_conductivity(tpsrhs_handle h, const double *x, double *sig
 }
 
 const char *tpsrhs_version(void) { return "tpsrhs 0.1.0 (gfx950)"; }
-
-}  // extern "C"
-
-namespace {
-// Forward Euler, RK2(a = 1) and RK3-SSP (time_integrators.hpp): the plain Mult (h->rk stays RkDev{}: k_flux writes the
-// residual, nothing enters the trace chain) and one k_rk_stage pass per stage.  (Fusing these combinations into k_flux's
-// epilogue, as RK4 has, is left out on purpose: DESIGN.md section 9.)  Here, after every other launch of this unit: see
-// the head of the time loop's section.
-template <int OP>
-void rk_stage(tpsrhs_operator *h, int64_t n, int64_t clamp_lo, int64_t clamp_hi, double dt, const double *dt_dev, double *x,
-              const double *k, double *y) {
-  const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
-  const int64_t items = vec ? (n + 1) / 2 : n;
-  const int grid = static_cast<int>(std::min<int64_t>((items + 255) / 256, 8192));  // the grid cap of k_rk4_stage
-  if (vec)
-    hipLaunchKernelGGL((k_rk_stage<OP, true, 256>), dim3(grid), dim3(256), 0, h->stream, n, clamp_lo, clamp_hi, dt, dt_dev, x, k, y,
-                       h->loop.d_nan.get());
-  else
-    hipLaunchKernelGGL((k_rk_stage<OP, false, 256>), dim3(grid), dim3(256), 0, h->stream, n, clamp_lo, clamp_hi, dt, dt_dev, x, k, y,
-                       h->loop.d_nan.get());
-  HIP_CHECK(hipGetLastError());
-}
-
-void rk_stages(tpsrhs_operator *h, int integrator, double *x, double dt, const double *dt_dev) {
-  const int64_t n = static_cast<int64_t>(h->neq) * h->ndofs;
-  const StageScratch sc = stage_scratch(h, n, true);
-  double *k = sc.k, *y = sc.y;
-  h->loop.chain.begin_step();  // every Mult of these schemes runs its own k_traces sweep
-  ScopeExit step([h](bool) { h->loop.chain.end_step(); });
-  // Check_Undershoot's rows, contiguous in [neq][ndofs]
-  const int64_t lo = h->loop.sp_first * h->ndofs, hi = h->loop.sp_last * h->ndofs;
-  h->launch(h, x, k, false);  // k = f(x); SetTime is a no-op for this operator
-  if (integrator == TPSRHS_FORWARD_EULER) {
-    rk_stage<RK_EULER>(h, n, lo, hi, dt, dt_dev, x, k, y);
-  } else if (integrator == TPSRHS_RK2) {
-    rk_stage<RK2_STAGE1>(h, n, lo, hi, dt, dt_dev, x, k, y);
-    h->launch(h, y, k, false);
-    rk_stage<RK2_STAGE2>(h, n, lo, hi, dt, dt_dev, x, k, y);
-  } else {
-    rk_stage<RK3_STAGE1>(h, n, lo, hi, dt, dt_dev, x, k, y);
-    h->launch(h, y, k, false);
-    rk_stage<RK3_STAGE2>(h, n, lo, hi, dt, dt_dev, x, k, y);
-    h->launch(h, y, k, false);
-    rk_stage<RK3_STAGE3>(h, n, lo, hi, dt, dt_dev, x, k, y);
-  }
-}
-}  // namespace
-
-// ---- running mean and velocity covariances (statistics.hpp) ----------------------------------------------------------------
-// After every other launch of this unit, as the integrators above.
-namespace {
-void stats_release(tpsrhs_operator *h) {
-  tpsrhs_stats_state *st = h->stats;
-  if (!st) return;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);  // a sample may still be running
-  delete st;
-  h->stats = nullptr;
-}
-
-template <int NVEL, bool VARI>
-void launch_stats_sample(tpsrhs_operator *h) {
-  tpsrhs_stats_state *st = h->stats;
-  const int64_t n = h->ndofs;
-  const double *prim = st->d_scratch.get(), *p = prim + h->neq * n;
-  double *mean = st->d_mean.get(), *vari = st->d_vari.get();
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(prim) | reinterpret_cast<uintptr_t>(mean) | reinterpret_cast<uintptr_t>(vari);
-  const bool vec = (n & 1) == 0 && (bits & 15) == 0;  // then every row of every array is 16-byte aligned, p included
-  const int64_t items = vec ? n / 2 : n;
-  const int grid = static_cast<int>(std::min<int64_t>((items + 255) / 256, 8192));  // the grid cap of k_rk_stage
-  if (grid == 0) return;
-  if (vec)
-    hipLaunchKernelGGL((k_stats_sample<NVEL, VARI, true, 256>), dim3(grid), dim3(256), 0, h->stream, h->neq, n, st->ns_mean,
-                       st->ns_vari, prim, p, mean, vari);
-  else
-    hipLaunchKernelGGL((k_stats_sample<NVEL, VARI, false, 256>), dim3(grid), dim3(256), 0, h->stream, h->neq, n, st->ns_mean,
-                       st->ns_vari, prim, p, mean, vari);
-  HIP_CHECK(hipGetLastError());
-}
-
-// One sample of the device vector x, stream-ordered: the primitives and the pressure from the gas model's own point-wise
-// kernel (tpsrhs_eval_pointwise quantities 0 and 1: no physics here), then the update.  The counters are host integers.
-void stats_sample(tpsrhs_operator *h, const double *x) {
-  tpsrhs_stats_state *st = h->stats;
-  const int64_t n = h->ndofs;
-  h->point_eval(h, 0, n, x, st->d_scratch.get());
-  h->point_eval(h, 1, n, x, st->d_scratch.get() + h->neq * n);
-  const bool vari = st->nvar > 0;
-  if (h->nvel == 3)
-    vari ? launch_stats_sample<3, true>(h) : launch_stats_sample<3, false>(h);
-  else
-    vari ? launch_stats_sample<2, true>(h) : launch_stats_sample<2, false>(h);
-  st->ns_mean++;
-  st->ns_vari++;
-}
-
-// the statistics of h, or NULL with the error text set
-tpsrhs_stats_state *stats_of(tpsrhs_handle h, const char *who) {
-  if (!h) {
-    fail(TPSRHS_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL handle");
-    return nullptr;
-  }
-  if (!h->stats) fail(TPSRHS_ERR_INVALID_ARGUMENT, std::string(who) + ": statistics are not configured (tpsrhs_stats_configure)");
-  return h->stats;
-}
-}  // namespace
-
-extern "C" {
-
-int tpsrhs_stats_configure(tpsrhs_handle h, int64_t sample_interval, int64_t start_iter, int compute_variances) {
-  if (!h) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_configure: NULL handle");
-  if (sample_interval < 0 || start_iter < 0)
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_configure: needs sample_interval >= 0 (0: off) and start_iter >= 0");
-  if (sample_interval > 0 && h->nvel != 2 && h->nvel != 3)
-    return fail(TPSRHS_ERR_UNSUPPORTED, "tpsrhs_stats_configure: two or three velocity components");
-  return guarded([&] {
-    stats_release(h);
-    if (sample_interval == 0) return;
-    HIP_CHECK(hipSetDevice(h->device));
-    std::unique_ptr<tpsrhs_stats_state> st(new tpsrhs_stats_state());
-    st->cadence.interval = sample_interval;
-    st->cadence.start = start_iter;
-    st->nvar = compute_variances ? h->nvel * (h->nvel + 1) / 2 : 0;
-    const int64_t n = h->ndofs;
-    st->d_mean = DevBuf<double>(h->neq * n);
-    if (st->nvar) st->d_vari = DevBuf<double>(st->nvar * n);
-    st->d_scratch = DevBuf<double>((h->neq + 1) * n);
-    HIP_CHECK(hipMemsetAsync(st->d_mean.get(), 0, sizeof(double) * h->neq * n, h->stream));
-    if (st->nvar) HIP_CHECK(hipMemsetAsync(st->d_vari.get(), 0, sizeof(double) * st->nvar * n, h->stream));
-    h->stats = st.release();  // complete: a call that throws above leaves the statistics off
-  });
-}
-
-int tpsrhs_stats_set_iter(tpsrhs_handle h, int64_t iter) {
-  tpsrhs_stats_state *st = stats_of(h, "tpsrhs_stats_set_iter");
-  if (!st) return TPSRHS_ERR_INVALID_ARGUMENT;
-  if (iter < 0) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_set_iter: needs iter >= 0");
-  st->cadence.count = iter;
-  return TPSRHS_OK;
-}
-
-int tpsrhs_stats_add_sample(tpsrhs_handle h, const double *x) {
-  if (!stats_of(h, "tpsrhs_stats_add_sample")) return TPSRHS_ERR_INVALID_ARGUMENT;
-  if (!x) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_add_sample: NULL argument");
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(h->device));
-    stats_sample(h, x);
-  });
-}
-
-int tpsrhs_stats_get(tpsrhs_handle h, double *mean_out, double *vari_out, int *ns_mean, int *ns_vari, int64_t *iter) {
-  tpsrhs_stats_state *st = stats_of(h, "tpsrhs_stats_get");
-  if (!st) return TPSRHS_ERR_INVALID_ARGUMENT;
-  if (vari_out && !st->nvar)
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_get: the covariances are not computed (compute_variances = 0)");
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(h->device));
-    const int64_t n = h->ndofs;
-    if (mean_out) HIP_CHECK(hipMemcpyAsync(mean_out, st->d_mean.get(), sizeof(double) * h->neq * n, hipMemcpyDeviceToDevice, h->stream));
-    if (vari_out) HIP_CHECK(hipMemcpyAsync(vari_out, st->d_vari.get(), sizeof(double) * st->nvar * n, hipMemcpyDeviceToDevice, h->stream));
-    if (ns_mean) *ns_mean = st->ns_mean;
-    if (ns_vari) *ns_vari = st->ns_vari;
-    if (iter) *iter = st->cadence.count;
-  });
-}
-
-int tpsrhs_stats_set(tpsrhs_handle h, const double *mean, const double *vari, int ns_mean, int ns_vari) {
-  tpsrhs_stats_state *st = stats_of(h, "tpsrhs_stats_set");
-  if (!st) return TPSRHS_ERR_INVALID_ARGUMENT;
-  if (ns_mean < 0 || ns_vari < 0 || (ns_mean > 0 && !mean))
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_set: needs counters >= 0 and the mean field of ns_mean > 0 samples");
-  if (vari && ns_vari > 0 && !st->nvar)
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_set: the covariances are not computed (compute_variances = 0)");
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(h->device));
-    const int64_t n = h->ndofs;
-    const bool keep_vari = vari && ns_vari > 0;  // else restartRMS: the covariances start again
-    if (ns_mean > 0)
-      HIP_CHECK(hipMemcpyAsync(st->d_mean.get(), mean, sizeof(double) * h->neq * n, hipMemcpyDeviceToDevice, h->stream));
-    else
-      HIP_CHECK(hipMemsetAsync(st->d_mean.get(), 0, sizeof(double) * h->neq * n, h->stream));
-    if (st->nvar) {
-      if (keep_vari)
-        HIP_CHECK(hipMemcpyAsync(st->d_vari.get(), vari, sizeof(double) * st->nvar * n, hipMemcpyDeviceToDevice, h->stream));
-      else
-        HIP_CHECK(hipMemsetAsync(st->d_vari.get(), 0, sizeof(double) * st->nvar * n, h->stream));
-    }
-    st->ns_mean = ns_mean;
-    st->ns_vari = keep_vari ? ns_vari : 0;
-  });
-}
-
-int tpsrhs_stats_num_variances(tpsrhs_handle h, int *num_variances) {
-  tpsrhs_stats_state *st = stats_of(h, "tpsrhs_stats_num_variances");
-  if (!st) return TPSRHS_ERR_INVALID_ARGUMENT;
-  if (!num_variances) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_stats_num_variances: NULL argument");
-  *num_variances = st->nvar;
-  return TPSRHS_OK;
-}
-
-}  // extern "C"
-
-// ---- point sampling and probe records (sampling.hpp, point_locate.hpp) --------------------------------------------------------
-// After every other launch of this unit, as the integrators and the statistics above.
-namespace {
-// What reading the probe records and reading the monitor records share.  The first n rows of one column of a log (`width`
-// doubles a row) to the host, on the operator's stream ...
-void fetch_rows(tpsrhs_operator *h, double *dst, const DevBuf<double> &col, int64_t n, int64_t width) {
-  if (dst && n * width) HIP_CHECK(hipMemcpyAsync(dst, col.get(), sizeof(double) * n * width, hipMemcpyDeviceToHost, h->stream));
-}
-// ... and, once the stream has been synchronised, the host half: the counters, the step of every record, the optional restart
-void read_index(RecordIndex &ix, int64_t *nrecords, int64_t *ndropped, int64_t *iters_out, int reset) {
-  if (nrecords) *nrecords = ix.nrecords;
-  if (ndropped) *ndropped = ix.ndropped;
-  if (iters_out && ix.nrecords) std::memcpy(iters_out, ix.iters.data(), sizeof(int64_t) * ix.nrecords);
-  if (reset) ix.reset();  // the buffer starts again; the step counter goes on
-}
-
-void probe_off(tpsrhs_operator *h) {
-  tpsrhs_sampling_state *ss = h->sampling;
-  if (!ss || !ss->probe.sampler) return;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);  // a record may still be running
-  ss->probe = tpsrhs_probe_log();
-}
-
-void sampling_release(tpsrhs_operator *h) {
-  tpsrhs_sampling_state *ss = h->sampling;
-  if (!ss) return;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);  // a sample may still be running
-  delete ss;
-  h->sampling = nullptr;
-}
-
-// The sources of tpsrhs_transfer that hold a cached sampler: the destruction of ANY operator looks here for samplers at
-// its nodes (the cache is keyed by the address of dst, which the next tpsrhs_create may hand out again).
-std::mutex g_transfer_mu;
-std::vector<tpsrhs_operator *> g_transfer_sources;
-
-void sampler_remove(tpsrhs_operator *h, tpsrhs_sampler *s);
-
-// h is being destroyed: forget it as a source (sampling_release frees its samplers) and drop every sampler at its nodes
-void transfer_release(tpsrhs_operator *h) {
-  std::lock_guard<std::mutex> lock(g_transfer_mu);
-  auto &src = g_transfer_sources;
-  src.erase(std::remove(src.begin(), src.end(), h), src.end());
-  for (tpsrhs_operator *o : src) {
-    auto &tr = o->sampling->transfers;  // exists: o holds a cached sampler
-    for (size_t k = tr.size(); k-- > 0;)
-      if (tr[k].dst == h) {
-        sampler_remove(o, tr[k].sampler);
-        tr.erase(tr.begin() + static_cast<std::ptrdiff_t>(k));
-      }
-  }
-}
-
-template <int DIM, int P>
-void launch_sample(tpsrhs_operator *h, const tpsrhs_sampler *s, const SampleNodes &nodes, int nrows, const double *field,
-                   double *out) {
-  constexpr int BLOCK = 64;  // one wave: 64 probes are one block, a plane of 65 536 points is 1024 blocks over the 256 CUs
-  const int64_t grid = (s->npts + BLOCK - 1) / BLOCK;
-  if (grid == 0) return;
-  if (grid >= (int64_t(1) << 31)) throw Unsupported("tpsrhs_sample: more than 2^37 points");
-  hipLaunchKernelGGL((k_sample<DIM, P, BLOCK>), dim3(static_cast<unsigned>(grid)), dim3(BLOCK), 0, h->stream, s->npts, nrows,
-                     h->ndofs, nodes, s->d_elem.get(), s->d_ref.get(), s->d_perm.get(), s->fill, field, out);
-  HIP_CHECK(hipGetLastError());
-}
-
-// out[nrows][npts] = field[nrows][NDofs] at the points of s, on the operator's stream
-void sample_field(tpsrhs_operator *h, const tpsrhs_sampler *s, int nrows, const double *field, double *out) {
-  SampleNodes nodes = {};
-  double wts[TPSRHS_MAXORDER + 1];
-  segment_rule01(h->nc, h->order + 1, nodes.x, wts);  // the nodes of the operator's basis, as make_tables places them
-  with_dim_order(h, "tpsrhs_sample", [&](auto dim, auto p) {
-    launch_sample<decltype(dim)::value, decltype(p)::value>(h, s, nodes, nrows, field, out);
-  });
-}
-
-// One probe record of the device vector x, stream-ordered, or one more dropped record when the buffer is full.
-void probe_record(tpsrhs_operator *h, const double *x) {
-  tpsrhs_probe_log &log = h->sampling->probe;
-  const int64_t r = log.index.claim(log.cadence.count);
-  if (r < 0) return;
-  const int64_t per = static_cast<int64_t>(h->neq) * log.sampler->npts;
-  sample_field(h, log.sampler, h->neq, x, log.d_values.get() + r * per);
-  HIP_CHECK(hipMemcpyAsync(log.d_times.get() + r, h->loop.d_ctl.get() + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-}
-
-// the position of s among the samplers of ss, or their end
-auto sampler_find(tpsrhs_sampling_state *ss, const tpsrhs_sampler *s) {
-  return std::find_if(ss->samplers.begin(), ss->samplers.end(), [s](const auto &u) { return u.get() == s; });
-}
-
-// s, a live sampler of h, leaves it
-void sampler_remove(tpsrhs_operator *h, tpsrhs_sampler *s) {
-  tpsrhs_sampling_state *ss = h->sampling;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);  // a sample may still be running
-  if (ss->probe.sampler == s) probe_off(h);
-  ss->samplers.erase(sampler_find(ss, s));
-}
-
-// The host copies of a device-located sampler (elem, ref, nfound), fetched once; synchronises the stream.
-void sampler_fetch(tpsrhs_sampler *s) {
-  if (s->host_valid) return;
-  tpsrhs_operator *h = s->owner;
-  HIP_CHECK(hipSetDevice(h->device));
-  unsigned long long nf = 0;
-  s->elem.resize(static_cast<size_t>(s->npts));
-  s->ref.resize(static_cast<size_t>(s->npts) * h->dim);
-  HIP_CHECK(hipMemcpyAsync(&nf, s->d_nfound.get(), sizeof(nf), hipMemcpyDeviceToHost, h->stream));
-  if (s->npts) {
-    HIP_CHECK(hipMemcpyAsync(s->elem.data(), s->d_elem.get(), s->elem.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipMemcpyAsync(s->ref.data(), s->d_ref.get(), s->ref.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  }
-  HIP_CHECK(hipStreamSynchronize(h->stream));
-  s->nfound = static_cast<int64_t>(nf);
-  s->host_valid = true;
-}
-// ... and the count alone (tpsrhs_transfer's num_missing): 8 bytes instead of the arrays
-int64_t sampler_nfound(tpsrhs_sampler *s) {
-  if (s->host_valid) return s->nfound;
-  tpsrhs_operator *h = s->owner;
-  unsigned long long nf = 0;
-  HIP_CHECK(hipMemcpyAsync(&nf, s->d_nfound.get(), sizeof(nf), hipMemcpyDeviceToHost, h->stream));
-  HIP_CHECK(hipStreamSynchronize(h->stream));
-  return static_cast<int64_t>(nf);
-}
-
-// The search grid of h's mesh for this tolerance on the device, built and uploaded at first use.
-template <int DIM>
-LocateGridView<DIM> device_grid(tpsrhs_operator *h, double tol) {
-  if (!h->sampling) h->sampling = new tpsrhs_sampling_state();
-  tpsrhs_sampling_state *ss = h->sampling;
-  tpsrhs_locate_grid_dev *g = nullptr;
-  for (const auto &c : ss->grids)
-    if (c->tol == tol) g = c.get();
-  if (!g) {
-    std::unique_ptr<tpsrhs_locate_grid_dev> up(new tpsrhs_locate_grid_dev());
-    up->tol = tol;
-    up->host = build_locate_grid<DIM>(h->ne, h->topo.verts.data(), tol);
-    up->d_lo = DevBuf<double>(up->host.lo);
-    up->d_hi = DevBuf<double>(up->host.hi);
-    up->d_start = DevBuf<int64_t>(up->host.start);
-    up->d_list = DevBuf<int32_t>(up->host.list);
-    for (auto *v : {&up->host.lo, &up->host.hi}) std::vector<double>().swap(*v);
-    std::vector<int64_t>().swap(up->host.start);
-    std::vector<int32_t>().swap(up->host.list);
-    g = up.get();
-    ss->grids.push_back(std::move(up));
-  }
-  return locate_grid_view<DIM>(g->host, g->d_lo.get(), g->d_hi.get(), g->d_start.get(), g->d_list.get());
-}
-
-template <int DIM>
-void launch_locate(tpsrhs_operator *h, tpsrhs_sampler *s, const double *xyz, double tol) {
-  constexpr int BLOCK = 64;
-  const int64_t grid = (s->npts + BLOCK - 1) / BLOCK;
-  if (grid >= (int64_t(1) << 31)) throw Unsupported("tpsrhs_sampler_create_device: more than 2^37 points");
-  const LocateGridView<DIM> g = device_grid<DIM>(h, tol);
-  HIP_CHECK(hipMemsetAsync(s->d_nfound.get(), 0, sizeof(unsigned long long), h->stream));
-  if (grid == 0) return;
-  hipLaunchKernelGGL((k_locate<DIM, BLOCK>), dim3(static_cast<unsigned>(grid)), dim3(BLOCK), 0, h->stream, g, h->d_verts.get(), s->npts,
-                     xyz, tol, s->d_elem.get(), s->d_ref.get(), s->d_perm.get(), s->d_nfound.get());
-  HIP_CHECK(hipGetLastError());
-}
-
-// a sampler of h at the DEVICE points xyz[dim][npts], located on h's stream; registered with h
-tpsrhs_sampler *sampler_create_device(tpsrhs_operator *h, int64_t npts, const double *xyz, double tol, double fill) {
-  if (h->ne <= 0) throw Unsupported("tpsrhs_sampler_create_device: the operator has no elements");
-  const double t = tol > 0.0 ? tol : LOCATE_DEFAULT_TOL;
-  std::unique_ptr<tpsrhs_sampler> s(new tpsrhs_sampler());
-  s->owner = h;
-  s->npts = npts;
-  s->fill = fill;
-  s->on_device = true;
-  s->host_valid = false;
-  s->d_elem = DevBuf<int32_t>(npts);
-  s->d_ref = DevBuf<double>(npts * h->dim);
-  s->d_perm = DevBuf<int64_t>(npts);
-  s->d_nfound = DevBuf<unsigned long long>(1);
-  if (h->dim == 2)
-    launch_locate<2>(h, s.get(), xyz, t);
-  else
-    launch_locate<3>(h, s.get(), xyz, t);
-  h->sampling->samplers.push_back(std::move(s));  // exists: device_grid made it
-  return h->sampling->samplers.back().get();
-}
-
-void node_coordinates_device(tpsrhs_operator *h, double *xyz_out, hipStream_t stream) {
-  SampleNodes nodes = {};
-  double wts[TPSRHS_MAXORDER + 1];
-  segment_rule01(h->nc, h->order + 1, nodes.x, wts);  // as sample_field
-  constexpr int BLOCK = 256;
-  const int64_t grid = (h->ndofs + BLOCK - 1) / BLOCK;
-  if (grid == 0) return;
-  if (grid >= (int64_t(1) << 31)) throw Unsupported("tpsrhs_node_coordinates: more than 2^39 nodes");
-  if (h->dim == 2)
-    hipLaunchKernelGGL((k_node_coordinates<2, BLOCK>), dim3(static_cast<unsigned>(grid)), dim3(BLOCK), 0, stream, h->ndofs,
-                       h->order + 1, nodes, h->d_verts.get(), xyz_out);
-  else
-    hipLaunchKernelGGL((k_node_coordinates<3, BLOCK>), dim3(static_cast<unsigned>(grid)), dim3(BLOCK), 0, stream, h->ndofs,
-                       h->order + 1, nodes, h->d_verts.get(), xyz_out);
-  HIP_CHECK(hipGetLastError());
-}
-
-// is s a live sampler?  (its owner is then s->owner)
-bool sampler_alive(const tpsrhs_sampler *s, const tpsrhs_operator *h) {
-  tpsrhs_sampling_state *ss = h ? h->sampling : nullptr;
-  return ss && sampler_find(ss, s) != ss->samplers.end();
-}
-}  // namespace
-
-extern "C" {
-
-int tpsrhs_locate_points(const tpsrhs_mesh *mesh, int64_t npts, const double *xyz, double tol, int32_t *elem_out,
-                         double *ref_out) {
-  const int st = locate_points(mesh, npts, xyz, tol, elem_out, ref_out);
-  if (st != TPSRHS_OK)
-    return fail(st, "tpsrhs_locate_points: needs a mesh of dim 2 or 3 with elem_coords, npts >= 0, non-NULL arrays and a tolerance that is a number");
-  return st;
-}
-
-int tpsrhs_plane_points(const double point[3], const double normal[3], const double bb0[3], const double bb1[3], int n,
-                        double *xyz_out) {
-  const int st = plane_points(point, normal, bb0, bb1, n, xyz_out);
-  if (st != TPSRHS_OK) return fail(st, "tpsrhs_plane_points: needs non-NULL arguments and n >= 2");
-  return st;
-}
-
-int tpsrhs_sampler_create(tpsrhs_handle h, int64_t npts, const double *xyz, double tol, double fill,
-                          tpsrhs_sampler_handle *out) {
-  if (out) *out = nullptr;
-  if (!h || !out || npts < 0 || (npts > 0 && !xyz) || std::isnan(tol))
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_sampler_create: needs a handle, npts >= 0, the points and a tolerance that is a number");
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(h->device));
-    const int dim = h->dim;
-    std::unique_ptr<tpsrhs_sampler> sp(new tpsrhs_sampler());
-    sp->owner = h;
-    sp->npts = npts;
-    sp->fill = fill;
-    sp->elem.assign(static_cast<size_t>(npts), -1);
-    sp->ref.assign(static_cast<size_t>(npts) * dim, 0.0);
-    // the operator's own host copy of the element vertices (Topology::verts, already in lexicographic corner order)
-    const double t = tol > 0.0 ? tol : LOCATE_DEFAULT_TOL;
-    if (dim == 2)
-      locate_points_lex<2>(h->ne, h->topo.verts.data(), npts, xyz, t, sp->elem.data(), sp->ref.data());
-    else
-      locate_points_lex<3>(h->ne, h->topo.verts.data(), npts, xyz, t, sp->elem.data(), sp->ref.data());
-    // sorted by element, ties in the caller's order, the points that were not found last
-    std::vector<int64_t> perm(static_cast<size_t>(npts));
-    for (int64_t i = 0; i < npts; i++) perm[static_cast<size_t>(i)] = i;
-    const std::vector<int32_t> &el = sp->elem;
-    std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) {
-      const int64_t ea = el[static_cast<size_t>(a)] < 0 ? int64_t(1) << 40 : el[static_cast<size_t>(a)];
-      const int64_t eb = el[static_cast<size_t>(b)] < 0 ? int64_t(1) << 40 : el[static_cast<size_t>(b)];
-      return ea < eb;
-    });
-    std::vector<int32_t> selem(static_cast<size_t>(npts));
-    std::vector<double> sref(static_cast<size_t>(npts) * dim);
-    for (int64_t k = 0; k < npts; k++) {
-      const int64_t i = perm[static_cast<size_t>(k)];
-      selem[static_cast<size_t>(k)] = el[static_cast<size_t>(i)];
-      if (el[static_cast<size_t>(i)] >= 0) sp->nfound++;
-      for (int d = 0; d < dim; d++) sref[static_cast<size_t>(k + d * npts)] = sp->ref[static_cast<size_t>(i + d * npts)];
-    }
-    sp->d_elem = DevBuf<int32_t>(selem);
-    sp->d_ref = DevBuf<double>(sref);
-    sp->d_perm = DevBuf<int64_t>(perm);
-    if (!h->sampling) h->sampling = new tpsrhs_sampling_state();
-    h->sampling->samplers.push_back(std::move(sp));
-    *out = h->sampling->samplers.back().get();
-  });
-}
-
-int tpsrhs_sampler_destroy(tpsrhs_sampler_handle s) {
-  if (!s) return TPSRHS_OK;
-  tpsrhs_operator *h = s->owner;
-  if (!sampler_alive(s, h)) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_sampler_destroy: not a sampler of a live operator");
-  sampler_remove(h, s);
-  return TPSRHS_OK;
-}
-
-int tpsrhs_sampler_info(tpsrhs_sampler_handle s, int64_t *npts, int64_t *nfound, int32_t *elem_out, double *ref_out) {
-  if (!s) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_sampler_info: NULL sampler");
-  if (!s->host_valid) {  // located on the device: the host copies come on demand
-    const int st = guarded([&] { sampler_fetch(s); });
-    if (st != TPSRHS_OK) return st;
-  }
-  if (npts) *npts = s->npts;
-  if (nfound) *nfound = s->nfound;
-  if (elem_out && s->npts) std::memcpy(elem_out, s->elem.data(), s->elem.size() * sizeof(int32_t));
-  if (ref_out && s->npts) std::memcpy(ref_out, s->ref.data(), s->ref.size() * sizeof(double));
-  return TPSRHS_OK;
-}
-
-int tpsrhs_sample(tpsrhs_sampler_handle s, int nrows, const double *field, double *out) {
-  if (!s || !field || !out || nrows < 1)
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_sample: needs a sampler, nrows >= 1 and non-NULL device arrays");
-  tpsrhs_operator *h = s->owner;
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(h->device));
-    sample_field(h, s, nrows, field, out);
-  });
-}
-
-int tpsrhs_sampler_create_device(tpsrhs_handle h, int64_t npts, const double *xyz, double tol, double fill,
-                                 tpsrhs_sampler_handle *out) {
-  if (out) *out = nullptr;
-  if (!h || !out || npts < 0 || (npts > 0 && !xyz) || std::isnan(tol))
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_sampler_create_device: needs a handle, npts >= 0, the device points and a tolerance that is a number");
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(h->device));
-    *out = sampler_create_device(h, npts, xyz, tol, fill);
-  });
-}
-
-int tpsrhs_node_coordinates(tpsrhs_handle h, double *xyz_out) {
-  if (!h || !xyz_out) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_node_coordinates: NULL argument");
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(h->device));
-    node_coordinates_device(h, xyz_out, h->stream);
-  });
-}
-
-int tpsrhs_transfer(tpsrhs_handle src, tpsrhs_handle dst, int nrows, const double *field_src, double *field_dst, double tol,
-                    double fill, int64_t *num_missing) {
-  if (!src || !dst || !field_src || !field_dst || nrows < 1 || std::isnan(tol))
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_transfer: needs two operators, nrows >= 1, non-NULL device arrays and a tolerance that is a number");
-  if (src->dim != dst->dim)
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_transfer: the operators differ in dim");
-  if (src->device != dst->device)
-    return fail(TPSRHS_ERR_UNSUPPORTED, "tpsrhs_transfer: the operators are on different devices");
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(src->device));
-    const double t = tol > 0.0 ? tol : LOCATE_DEFAULT_TOL;
-    tpsrhs_sampler *s = nullptr;
-    {
-      std::lock_guard<std::mutex> lock(g_transfer_mu);
-      if (src->sampling)
-        for (const tpsrhs_transfer_entry &e : src->sampling->transfers)
-          if (e.dst == dst && e.tol == t) s = e.sampler;
-      if (s) {
-        src->sampling->num_cache_hits++;
-      } else {
-        // the nodes of dst, on src's stream (they depend on nothing dst's stream writes), live until they are located
-        const DevBuf<double> xyz(static_cast<size_t>(dst->ndofs) * dst->dim);
-        node_coordinates_device(dst, xyz.get(), src->stream);
-        s = sampler_create_device(src, dst->ndofs, xyz.get(), t, fill);
-        HIP_CHECK(hipStreamSynchronize(src->stream));  // once per pair: xyz is freed below
-        src->sampling->transfers.push_back({dst, t, s});
-        src->sampling->num_located++;
-        if (std::find(g_transfer_sources.begin(), g_transfer_sources.end(), src) == g_transfer_sources.end())
-          g_transfer_sources.push_back(src);
-      }
-    }
-    s->fill = fill;
-    sample_field(src, s, nrows, field_src, field_dst);
-    if (dst->stream != src->stream) {  // dst's stream reads field_dst after this
-      hipEvent_t ev;
-      HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      hipError_t e1 = hipEventRecord(ev, src->stream);
-      hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(dst->stream, ev, 0) : e1;
-      (void)hipEventDestroy(ev);  // released when the record has completed
-      HIP_CHECK(e2);
-    }
-    if (num_missing) *num_missing = s->npts - sampler_nfound(s);
-  });
-}
-
-int tpsrhs_transfer_stats(tpsrhs_handle src, int64_t *num_located, int64_t *num_cache_hits) {
-  if (!src) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_transfer_stats: NULL handle");
-  const tpsrhs_sampling_state *ss = src->sampling;
-  if (num_located) *num_located = ss ? ss->num_located : 0;
-  if (num_cache_hits) *num_cache_hits = ss ? ss->num_cache_hits : 0;
-  return TPSRHS_OK;
-}
-
-int tpsrhs_probe_configure(tpsrhs_handle h, tpsrhs_sampler_handle s, int64_t interval, int64_t capacity) {
-  if (!h) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_probe_configure: NULL handle");
-  if (interval < 0 || capacity < 0)
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_probe_configure: needs interval >= 0 (0: off) and capacity >= 0");
-  const bool on = s != nullptr && interval > 0;
-  if (on && capacity < 1) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_probe_configure: needs capacity >= 1");
-  if (on && (s->owner != h || !sampler_alive(s, h)))
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_probe_configure: the sampler belongs to another operator");
-  return guarded([&] {
-    probe_off(h);
-    if (!on) return;
-    HIP_CHECK(hipSetDevice(h->device));
-    tpsrhs_probe_log log;
-    log.sampler = s;
-    log.cadence.interval = interval;
-    log.index.capacity = capacity;
-    log.d_values = DevBuf<double>(capacity * h->neq * s->npts);
-    log.d_times = DevBuf<double>(capacity);
-    loop_ctl(h);  // a record copies the time from there
-    // complete: a call that throws above leaves the probes off.  (h->sampling exists: s is one of its samplers)
-    h->sampling->probe = std::move(log);
-  });
-}
-
-int tpsrhs_probe_read(tpsrhs_handle h, int64_t *nrecords, int64_t *ndropped, int64_t *iters_out, double *times_out,
-                      double *values_out, int reset) {
-  if (!h) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_probe_read: NULL handle");
-  tpsrhs_sampling_state *ss = h->sampling;
-  if (!ss || !ss->probe.sampler) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_probe_read: probes are not configured (tpsrhs_probe_configure)");
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(h->device));
-    tpsrhs_probe_log &log = ss->probe;
-    fetch_rows(h, times_out, log.d_times, log.index.nrecords, 1);
-    fetch_rows(h, values_out, log.d_values, log.index.nrecords, static_cast<int64_t>(h->neq) * log.sampler->npts);
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    read_index(log.index, nrecords, ndropped, iters_out, reset);
-  });
-}
-
-}  // extern "C"
-
-// ---- the wall-distance function (wall_faces.hpp, wall_distance.hpp) -----------------------------------------------------------
-// After every other launch of this unit, as the integrators, the statistics and the sampling above.  No operator state: the
-// face table lives on the device for the length of one call.
-namespace {
-template <int DIM>
-void launch_wall_distance(tpsrhs_operator *h, int64_t nfaces, const double *face_xyz, double *out) {
-  std::vector<double> coef;
-  wd_face_table<DIM>(nfaces, face_xyz, coef);
-  WdNodes nodes = {};
-  double wts[TPSRHS_MAXORDER + 1];
-  segment_rule01(h->nc, h->order + 1, nodes.x, wts);  // the nodes of the operator's basis, as make_tables places them
-  const int64_t grid = (h->ndofs + WD_BLOCK - 1) / WD_BLOCK;
-  if (grid == 0) return;
-  if (grid >= (int64_t(1) << 31)) throw Unsupported("tpsrhs_wall_distance: more than 2^39 nodes");
-  const char *env = std::getenv("TPSRHS_WALLDIST_CULL");
-  const bool cull = !(env && env[0] == '0');
-  const DevBuf<double> table(coef);
-  const dim3 g(static_cast<unsigned>(grid)), b(WD_BLOCK);
-  if (cull)
-    hipLaunchKernelGGL((k_wall_distance<DIM, true>), g, b, 0, h->stream, h->ndofs, h->order + 1, nodes, h->d_verts.get(), nfaces,
-                       table.get(), out);
-  else
-    hipLaunchKernelGGL((k_wall_distance<DIM, false>), g, b, 0, h->stream, h->ndofs, h->order + 1, nodes, h->d_verts.get(), nfaces,
-                       table.get(), out);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipStreamSynchronize(h->stream));  // the table is freed on return
-}
-}  // namespace
-
-extern "C" {
-
-int tpsrhs_wall_faces(const tpsrhs_mesh *mesh, int num_bcs, const tpsrhs_bc *bcs, int num_attributes, const int *attributes,
-                      int64_t capacity, double *face_xyz_out, int64_t *num_faces_out) {
-  const int st = wall_faces(mesh, num_bcs, bcs, num_attributes, attributes, capacity, face_xyz_out, num_faces_out);
-  if (st != TPSRHS_OK)
-    return fail(st, "tpsrhs_wall_faces: needs a mesh of dim 2 or 3 whose boundary records are faces of its elements, the attribute list or the boundary conditions, capacity >= 0 with its array, and num_faces_out");
-  return st;
-}
-
-int tpsrhs_wall_distance(tpsrhs_handle h, int64_t num_faces, const double *face_xyz, double *distance_out) {
-  if (!h || !distance_out || num_faces < 0 || (num_faces > 0 && !face_xyz))
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_wall_distance: needs a handle, num_faces >= 0, the faces and the output array");
-  const int64_t nval = num_faces * (int64_t(1) << (h->dim - 1)) * h->dim;
-  for (int64_t i = 0; i < nval; i++)
-    if (!std::isfinite(face_xyz[i]))
-      return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_wall_distance: face coordinate " + std::to_string(i) + " is not finite");
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(h->device));
-    if (h->dim == 3)
-      launch_wall_distance<3>(h, num_faces, face_xyz, distance_out);
-    else
-      launch_wall_distance<2>(h, num_faces, face_xyz, distance_out);
-  });
-}
-
-}  // extern "C"
-
-// ---- volume integrals, nodal extrema and the monitor records (quadrature_points.hpp, integrals.hpp) -------------------------
-// After every other launch of this unit, as the integrators, the statistics, the sampling and the wall distance above.
-namespace {
-void monitor_off(tpsrhs_operator *h) {
-  tpsrhs_integrals_state *is = h->integrals;
-  if (!is || !is->monitor.cadence.interval) return;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);  // a record may still be running
-  is->monitor = tpsrhs_monitor_log();
-}
-
-void integrals_release(tpsrhs_operator *h) {
-  tpsrhs_integrals_state *is = h->integrals;
-  if (!is) return;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);  // a reduction may still be running
-  delete is;
-  h->integrals = nullptr;
-}
-
-// a grid of at most INTEG_MAXBLOCKS blocks over ne elements in batches of eb: -> (blocks, elements per block)
-void reduction_grid(int ne, int eb, int *blocks, int *run) {
-  const int batches = (ne + eb - 1) / eb;
-  const int per = std::max(1, (batches + INTEG_MAXBLOCKS - 1) / INTEG_MAXBLOCKS);
-  *run = per * eb;
-  *blocks = std::max(1, (batches + per - 1) / per);
-}
-
-// the state with its scratch, sized once: the grids depend on the mesh and the order only
-tpsrhs_integrals_state *integrals_of(tpsrhs_operator *h) {
-  if (h->integrals) return h->integrals;
-  int eb = 0;
-  with_dim_order(h, "tpsrhs_integrate", [&](auto dim, auto p) { eb = IntegCfg<decltype(dim)::value, decltype(p)::value>::EB; });
-  std::unique_ptr<tpsrhs_integrals_state> is(new tpsrhs_integrals_state());
-  is->integ_eb = eb;
-  reduction_grid(h->ne, eb, &is->integ_blocks, &is->integ_run);
-  const int npe = static_cast<int>(h->ndofs / std::max(h->ne, 1));
-  is->stat_lpe = lanes_per_element(npe);
-  reduction_grid(h->ne, 64 / is->stat_lpe, &is->stat_blocks, &is->stat_run);
-  const int64_t per_row = std::max<int64_t>(2 * static_cast<int64_t>(is->integ_blocks) * eb,
-                                             3 * static_cast<int64_t>(is->stat_blocks) * (64 / is->stat_lpe));
-  is->d_partial = DevBuf<double>(INTEG_ROWS * per_row);
-  h->integrals = is.release();
-  return h->integrals;
-}
-
-template <int DIM, int P>
-void launch_integrate(tpsrhs_operator *h, const tpsrhs_integrals_state *is, const QuadTab &tab, int nrows, const double *field,
-                      const double *exact, int radial, double *partial) {
-  typedef IntegCfg<DIM, P> C;
-  hipLaunchKernelGGL((k_integrate<DIM, P>), dim3(is->integ_blocks), dim3(64), 0, h->stream, h->ne, is->integ_run, nrows, h->ndofs,
-                     static_cast<int64_t>(h->ne) * C::NQD, radial, tab, h->d_verts.get(), field, exact, partial);
-  HIP_CHECK(hipGetLastError());
-}
-
-// sum_out[nrows], sumsq_out[nrows] (either may be NULL) of field[nrows][NDofs] - exact[nrows][npts], on the operator's stream
-void integrate_field(tpsrhs_operator *h, int nrows, const double *field, const double *exact, int radial, double *sum_out,
-                     double *sumsq_out) {
-  tpsrhs_integrals_state *is = integrals_of(h);
-  if (h->ne == 0) {
-    if (sum_out) HIP_CHECK(hipMemsetAsync(sum_out, 0, sizeof(double) * nrows, h->stream));
-    if (sumsq_out) HIP_CHECK(hipMemsetAsync(sumsq_out, 0, sizeof(double) * nrows, h->stream));
-    return;
-  }
-  QuadTab tab = {};
-  const int n1 = h->order + 1, nq = quad_points_1d(h->order);
-  double nodes[TPSRHS_MAXORDER + 1], wts[TPSRHS_MAXORDER + 1];
-  segment_rule01(h->nc, n1, nodes, wts);  // the nodes of the operator's basis, as make_tables places them
-  gauss_legendre01(nq, tab.g, tab.w);
-  for (int q = 0; q < nq; q++)
-    for (int a = 0; a < n1; a++) tab.B[q * n1 + a] = lagrange(nodes, n1, a, tab.g[q]);
-  const int64_t npts = static_cast<int64_t>(h->ne) * (h->dim == 3 ? nq * nq * nq : nq * nq);
-  const int64_t np = static_cast<int64_t>(is->integ_blocks) * is->integ_eb;
-  for (int r0 = 0; r0 < nrows; r0 += INTEG_ROWS) {  // the stream orders the launches: one scratch serves every slab of rows
-    const int nr = std::min(INTEG_ROWS, nrows - r0);
-    const double *f = field + r0 * h->ndofs, *ex = exact ? exact + r0 * npts : nullptr;
-    with_dim_order(h, "tpsrhs_integrate", [&](auto dim, auto p) {
-      launch_integrate<decltype(dim)::value, decltype(p)::value>(h, is, tab, nr, f, ex, radial, is->d_partial.get());
-    });
-    hipLaunchKernelGGL(k_integrate_final<1024>, dim3(1), dim3(1024), 0, h->stream, nr, np, is->d_partial.get(),
-                       sum_out ? sum_out + r0 : nullptr, sumsq_out ? sumsq_out + r0 : nullptr);
-    HIP_CHECK(hipGetLastError());
-  }
-}
-
-void nodal_stats_field(tpsrhs_operator *h, int nrows, const double *field, double *min_out, double *max_out, double *meanabs_out) {
-  tpsrhs_integrals_state *is = integrals_of(h);
-  const int npe = static_cast<int>(h->ndofs / std::max(h->ne, 1));
-  const int64_t np = static_cast<int64_t>(is->stat_blocks) * (64 / is->stat_lpe);
-  for (int r0 = 0; r0 < nrows; r0 += INTEG_ROWS) {
-    const int nr = std::min(INTEG_ROWS, nrows - r0);
-    // (ne == 0: one block without elements writes the empty partials +inf, -inf, 0)
-    hipLaunchKernelGGL(k_nodal_stats, dim3(is->stat_blocks, nr), dim3(64), 0, h->stream, h->ne, is->stat_run, npe, is->stat_lpe,
-                       h->ndofs, field + r0 * h->ndofs, is->d_partial.get());
-    HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_nodal_stats_final<1024>, dim3(1), dim3(1024), 0, h->stream, nr, np, h->ndofs, is->d_partial.get(),
-                       min_out ? min_out + r0 : nullptr, max_out ? max_out + r0 : nullptr,
-                       meanabs_out ? meanabs_out + r0 : nullptr);
-    HIP_CHECK(hipGetLastError());
-  }
-}
-
-// One monitor record of the device vector x, stream-ordered, or one more dropped record when the buffer is full.
-void monitor_record(tpsrhs_operator *h, const double *x) {
-  tpsrhs_monitor_log &log = h->integrals->monitor;
-  const int64_t r = log.index.claim(log.cadence.count);
-  if (r < 0) return;
-  const int axisym = h->dim == 2 && h->nvel == 3;
-  integrate_field(h, h->neq, x, nullptr, axisym, log.d_totals.get() + r * h->neq, nullptr);
-  nodal_stats_field(h, h->neq, x, log.d_mins.get() + r * h->neq, log.d_maxs.get() + r * h->neq, nullptr);
-  // {dt of the next step, time}: the loop's control block, which the variable-dt loop never has on the host
-  HIP_CHECK(hipMemcpyAsync(log.d_dts.get() + r, h->loop.d_ctl.get(), sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  HIP_CHECK(hipMemcpyAsync(log.d_times.get() + r, h->loop.d_ctl.get() + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-}
-}  // namespace
-
-extern "C" {
-
-int tpsrhs_quadrature_points(const tpsrhs_mesh *mesh, int order, double *xyz_out, double *w_out, int64_t *npts_out) {
-  const int st = quadrature_points(mesh, order, xyz_out, w_out, npts_out);
-  if (st != TPSRHS_OK)
-    return fail(st, "tpsrhs_quadrature_points: needs a mesh of dim 2 or 3 with elem_coords, an order in 1..5 and npts_out");
-  return st;
-}
-
-int tpsrhs_integrate(tpsrhs_handle h, int nrows, const double *field, const double *exact_q, int radial_weight,
-                     double *sum_out, double *sumsq_out) {
-  if (!h || !field || nrows < 1)
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_integrate: needs a handle, nrows >= 1 and the device field");
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(h->device));
-    integrate_field(h, nrows, field, exact_q, radial_weight ? 1 : 0, sum_out, sumsq_out);
-  });
-}
-
-int tpsrhs_nodal_stats(tpsrhs_handle h, int nrows, const double *field, double *min_out, double *max_out, double *meanabs_out) {
-  if (!h || !field || nrows < 1)
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_nodal_stats: needs a handle, nrows >= 1 and the device field");
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(h->device));
-    nodal_stats_field(h, nrows, field, min_out, max_out, meanabs_out);
-  });
-}
-
-int tpsrhs_monitor_configure(tpsrhs_handle h, int64_t interval, int64_t capacity) {
-  if (!h) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_monitor_configure: NULL handle");
-  if (interval < 0 || capacity < 0)
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_monitor_configure: needs interval >= 0 (0: off) and capacity >= 0");
-  if (interval > 0 && capacity < 1) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_monitor_configure: needs capacity >= 1");
-  return guarded([&] {
-    monitor_off(h);
-    if (interval == 0) return;
-    HIP_CHECK(hipSetDevice(h->device));
-    tpsrhs_integrals_state *is = integrals_of(h);  // with the scratch: a record allocates nothing
-    tpsrhs_monitor_log log;
-    log.cadence.interval = interval;
-    log.index.capacity = capacity;
-    log.d_times = DevBuf<double>(capacity);
-    log.d_dts = DevBuf<double>(capacity);
-    log.d_totals = DevBuf<double>(capacity * h->neq);
-    log.d_mins = DevBuf<double>(capacity * h->neq);
-    log.d_maxs = DevBuf<double>(capacity * h->neq);
-    loop_ctl(h);  // a record copies dt and the time from there
-    is->monitor = std::move(log);  // complete: a call that throws above leaves the monitor off
-  });
-}
-
-int tpsrhs_monitor_read(tpsrhs_handle h, int64_t *nrecords, int64_t *ndropped, int64_t *iters_out, double *times_out,
-                        double *dts_out, double *totals_out, double *mins_out, double *maxs_out, int reset) {
-  if (!h) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_monitor_read: NULL handle");
-  tpsrhs_integrals_state *is = h->integrals;
-  if (!is || !is->monitor.cadence.interval)
-    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_monitor_read: the monitor is not configured (tpsrhs_monitor_configure)");
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(h->device));
-    tpsrhs_monitor_log &log = is->monitor;
-    const int64_t n = log.index.nrecords;
-    fetch_rows(h, times_out, log.d_times, n, 1);
-    fetch_rows(h, dts_out, log.d_dts, n, 1);
-    fetch_rows(h, totals_out, log.d_totals, n, h->neq);
-    fetch_rows(h, mins_out, log.d_mins, n, h->neq);
-    fetch_rows(h, maxs_out, log.d_maxs, n, h->neq);
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    read_index(log.index, nrecords, ndropped, iters_out, reset);
-  });
-}
 
 }  // extern "C"
 

@@ -6,8 +6,8 @@
 // The trace chain.  k_flux of RK4 stages 1..3 forms the next stage's traces in its epilogue (RkDev::ta_out, kernels.hpp),
 // so the next Mult starts at k_gradient; inside an advance stage 4 does the same for the next step's stage 1 (`chained`),
 // because nothing touches x between two steps of one call.  There are two buffers, named by index: 0 is the operator's
-// d_TA, 1 its d_TA2 (allocated at first use).  A Mult that reads one writes the other.  Only launch_all (operator.hpp) asks
-// mult(); the stage functions and advance_with (tpsrhs.hip) make the transitions; nothing else writes the flags.
+// d_TA, 1 its d_TA2 (allocated at first use).  A Mult that reads one writes the other.  Only launch_all (launch.hpp) asks
+// mult(); the stage functions and advance_with (time_loop.hip) make the transitions; nothing else writes the flags.
 //   - Even number of swaps: a chained step hands over four times (stages 1..4), so it starts by reading buffer 0 and ends
 //     by writing buffer 0 -- every step of an advance, and so every replay of a captured step, sees the buffers as the
 //     captured one did.  A lone step hands over three times and leaves nothing valid.

@@ -1,5 +1,5 @@
 // The refusal of a configuration outside the built scope (-> TPSRHS_ERR_UNSUPPORTED).  No HIP in here: thrown by the
-// device-free plan (operator_plan.hpp) as well as by the library proper (operator.hpp).  plasma_params_host.hpp keeps a
+// device-free plan (operator_plan.hpp) as well as by the library proper (status.hpp, which every unit of it includes).  plasma_params_host.hpp keeps a
 // type of its own, UnsupportedConfig, which tpsrhs.hip translates: tests/host_physics builds that header from a copy, in a
 // directory that holds the physics headers alone.
 #ifndef TPSRHS_UNSUPPORTED_HPP_

@@ -17,13 +17,11 @@
 
 #include <cstdint>
 
+#include "kernel_args.hpp"
+
 namespace tpsrhs {
 
 enum { VIS_SPECIES = 0, VIS_FLUX = 1, VIS_SIGMA = 2, VIS_SOURCE = 3, VIS_NUM_GROUPS = 4 };
-
-struct VisRows {  // first row of each group (AuxiliaryVisualizationIndexes, in rows)
-  int Xsp, Ysp, nsp, FluxTrns, diffVel, SrcTrns, SpeciesTrns, rxn;
-};
 
 template <class PH, int GROUP>
 __global__ __launch_bounds__(256) void k_vis_fields(typename PH::KArg prm_k, VisRows rows, int64_t n,

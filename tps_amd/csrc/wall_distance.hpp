@@ -1,6 +1,6 @@
 // The wall-distance function on the device: distance from every DG node to the nearest wall boundary face, what the
 // reference computes at start-up with evaluateDistanceSerial (src/utils.cpp:371-514; called from src/M2ulPhyS.cpp:371-437
-// when flow/computeDistance is set) in one serial host loop over nodes x wall faces.  Included by tpsrhs.hip only: the
+// when flow/computeDistance is set) in one serial host loop over nodes x wall faces.  Included by wall_distance.hip only: the
 // kernel families do not see it.  The host half -- which faces are walls -- is wall_faces.hpp.
 //
 // A face is X(s, t) = a + b s + c t + d s t on [0,1]^2 (3-D; a = X00, b = X10 - X00, c = X01 - X00, d = X11 - X10 - X01 + X00
