@@ -30,6 +30,7 @@
 #include "basis.hpp"
 #include "kernel_args.hpp"
 #include "physics_dryair.hpp"
+#include "tab_image.hpp"
 
 namespace tpsrhs {
 
@@ -157,57 +158,6 @@ __device__ inline void block_sync() {
   }
 }
 
-// NC_ = 0: Gauss-Legendre basis + Gauss-Legendre rules (basisType 0, integrationRule 0): nodes and volume
-//          quadrature points coincide, diagonal mass matrix -- the pair of the reference's cylinder / wedge / torch inputs;
-// NC_ = 1: Gauss-Lobatto basis + Gauss-Lobatto rules (1, 1; the reference's defaults, src/M2ulPhyS.cpp:2671-2672):
-//          p+2 volume points per direction, dense element mass matrix, every integral through quadrature points.
-template <int DIM_, int P_, int NC_ = 0>
-struct Cfg {
-  static constexpr int DIM = DIM_, P = P_, N1 = P_ + 1, NC = NC_;
-  static constexpr int NPE = (DIM_ == 3) ? N1 * N1 * N1 : N1 * N1;
-  static constexpr int NF = (DIM_ == 3) ? N1 * N1 : N1;  // nodes of a face = lines through the element
-  static constexpr int Q1 = ((DIM_ - 1) + 2 * P_) / 2 + 1 + NC_;  // face rule, order OrderW + 2p
-  static constexpr int QV = P_ + 1 + NC_;                          // volume rule, order 2p
-  static constexpr int NQV = (DIM_ == 3) ? QV * QV * QV : QV * QV;
-  static constexpr int NQ = (DIM_ == 3) ? Q1 * Q1 : Q1;
-  static constexpr int NW = (DIM_ == 3) ? Q1 * N1 : 1;  // half-interpolated face values (3-D only)
-  static constexpr int NFACES = 2 * DIM_;
-  static constexpr int NV = 1 << DIM_;
-  // (the Gauss-Lobatto hexes of p = 2, 3 get two waves: their 100 / 72 face quadrature points per direction pair then
-  // are ONE round of the block's lanes -- see EPB below)
-  static constexpr int BLOCK = (NC_ && DIM_ == 3 && P_ >= 2) ? 128 : ((NPE <= 64) ? 64 : ((NPE <= 128) ? 128 : 256));
-  // elements per block.  3-D p = 1: 3 elements = 54 face quadrature points per direction pair, one round of the
-  // 64 lanes (4 elements needed a second round for 8 points, and with 11 equations that instantiation kept
-  // 2 x 3 sets of prefetched traces live: 259 spilled VGPRs); the non-collocated pair has 16 points per face: 2
-  // elements = 64 points, one round.  Round 2 ran that pair with 4 elements -- two rounds of face points in one wave,
-  // the shape of round 2's failing 11-equation kernel -- and in round 3 the mixtures of 9+ equations with the argon
-  // mixture transport returned a wrong species residual in the lanes of the block's third and fourth element, one of
-  // them a memory fault (tools/probe_gll_p1.py): that shape is gone.
-  // Every failing instantiation of rounds 2 and 3 had the same shape -- a single-wave block that takes TWO rounds of face
-  // quadrature points (and then more than 256 registers with SGPR spills) --, and no other shape has failed in the
-  // exhaustive sweep (tools/sweep_instantiations.py): in 3-D no block takes a second round any more.  Gauss-Lobatto
-  // pair: p = 1: 2 hexes x 2 faces x 16 points = 64; p = 2: 2 hexes, 100 points, 128 lanes; p = 3: 1 hex, 72 points,
-  // 128 lanes.  2-D, Gauss-Lobatto p = 1: 10 quads (60 points; 16 quads = 96 before).
-  static constexpr int EPB = (DIM_ == 3 && NC_) ? (P_ == 3 ? 1 : 2)
-                             : (DIM_ == 3 && P_ == 1) ? 3
-                             : (DIM_ == 2 && NC_ && P_ == 1) ? 10
-                                                             : BLOCK / NPE;
-  static constexpr int NODES = EPB * NPE;
-  // one direction pair (faces 2d, 2d+1) of a block
-  static constexpr int PF = 2 * EPB;
-  static constexpr int TN = PF * NF;
-  static constexpr int TW = PF * NW;
-  static constexpr int TQ = PF * NQ;
-  static constexpr int LN = EPB * NF;
-  static constexpr int Q_ROUNDS = (TQ + BLOCK - 1) / BLOCK;
-  static_assert(DIM_ == 2 || Q_ROUNDS == 1, "3-D: one round of face quadrature points per direction pair");
-  static_assert(!(DIM_ == 2 && NC_) || Q_ROUNDS == 1, "2-D Gauss-Lobatto pair: one round per direction pair");
-  // 2-D: the quadrature points of BOTH direction pairs of a block are worked on together (at p = 3 they
-  // are 2 x 32 = one full 64-lane round; one pair at a time leaves half of the lanes idle in the physics)
-  static constexpr int TQ2 = 2 * TQ;
-  static constexpr int Q2_ROUNDS = (TQ2 + BLOCK - 1) / BLOCK;
-};
-
 // Which sweeps take the Coulomb fits of their closure from the polynomial table (PlasmaPhys::transport_coeffs<CTAB>): the
 // argon-minimal ternary physics at 3-D, p = 3, collocated -- k_gradient's face points and k_flux's nodes, in either form of
 // the lean face kernel (the key does not look at TPSRHS_LEAN_GENERAL: the two forms stay bit-identical).
@@ -250,13 +200,84 @@ struct CoulombWin<C, PH, W, true> {
   static constexpr int DOUBLES = type::DOUBLES;
 };
 
-// LDS copy of the tables that are indexed per lane
+// Staged prologue.  load_face_info / load_tables / load_vertices are one exec-masked region per member group, each with its
+// own fetch of c_tab's address, a global load and a wait for EVERYTHING in flight (the counter of the vector memory loads
+// is in order, so the first of them also drains the nodal loads issued ahead of it): seven round trips, one after the
+// other, before a block's first neighbour gather.  The kernels named by staged_prologue() read instead a packed image of
+// Tab<C> that the host builds once (tab_image.hpp; 1 / w is computed there), together with the vertices and the face records,
+// with unconditional loads at clamped indices that go out AHEAD of the nodal loads: one round trip, and the LDS writes
+// that follow wait for these few loads alone.  -DTPSRHS_STAGED_PROLOGUE=0: the loaders above everywhere.
+#ifndef TPSRHS_STAGED_PROLOGUE
+#define TPSRHS_STAGED_PROLOGUE 1
+#endif
+typedef Cfg<3, 3, 0> StagedCfg;  // the one configuration the image is kept for
+static __constant__ Tab<StagedCfg> c_tab_image;
+template <class PH>
+struct plain_dry_air : std::false_type {};
+template <>
+struct plain_dry_air<DryAirPhys<3, false, false>> : std::true_type {};
+// the one-hex-per-wave blocks of the 3-D collocated p = 3 sweeps: the metric's family (k_gradient and k_flux) and dry air
+// (cfg2 / cfg4; k_flux alone: its k_gradient is on the list of kernels with a private segment, tests/golden/
+// spill_allowlist.txt, and would leave it with the staged prologue -- a kernel that gains or loses an entry there keeps the
+// loaders)
+enum { SWEEP_GRADIENT = 1, SWEEP_FLUX = 2 };
+template <class C, class PH, int SWEEP>
+constexpr bool staged_prologue() {
+  return TPSRHS_STAGED_PROLOGUE && std::is_same<C, StagedCfg>::value &&
+         (lean_one_hex<PH>::value || (plain_dry_air<PH>::value && SWEEP == SWEEP_FLUX));
+}
 template <class C>
-struct Tab {
-  double x[C::N1], w[C::N1], iw[C::N1], D[C::N1 * C::N1], b0[C::N1], b1[C::N1];
-  double xq[C::Q1], wq[C::Q1], B[C::Q1 * C::N1];
-  double xv[C::QV], wv[C::QV];  // volume rule (read by the non-collocated variant)
+struct StagedRegs {
+  static_assert(C::EPB == 1 && C::NODES == C::BLOCK, "one element per block, one lane per node");
+  static constexpr int NT = sizeof(Tab<C>) / sizeof(double), PER = C::NV * C::DIM;
+  static constexpr int TR = (NT + C::BLOCK - 1) / C::BLOCK;
+  static_assert(PER <= C::BLOCK && C::NFACES <= C::BLOCK, "one round of vertices and of face records");
+  double t[TR], v;
+  int2 f;
 };
+// every small load of the block, into registers; no lane is masked (the indices are clamped instead)
+template <class C>
+__device__ inline void stage_issue(StagedRegs<C> &r, const MeshDev &m, int e0) {
+  typedef StagedRegs<C> R;
+  const int tid = threadIdx.x;
+  // the image through a pointer to GLOBAL memory whose origin the compiler does not see (as fresh_table): a load from the
+  // constant address space is tied to no point of the program and moves past the fence below
+  typedef const double __attribute__((address_space(1))) *GP;
+  const unsigned long long a = reinterpret_cast<unsigned long long>(&c_tab_image);
+  unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(a));
+  unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(a >> 32));
+  asm volatile("" : "+s"(lo), "+s"(hi));
+  const GP img = reinterpret_cast<GP>((static_cast<unsigned long long>(hi) << 32) | lo);
+#pragma unroll
+  for (int k = 0; k < R::TR; k++) r.t[k] = img[min(tid + k * C::BLOCK, R::NT - 1)];
+  const int e = min(e0, m.ne - 1);  // (a block past the end of the mesh reads the last element's and keeps none of it)
+  r.v = (m.verts + static_cast<int64_t>(e) * R::PER)[min(tid, R::PER - 1)];
+  r.f = (m.face_info + static_cast<int64_t>(e) * C::NFACES)[min(tid, C::NFACES - 1)];
+  // (the instruction scheduler otherwise moves some of them behind the nodal loads that follow in the same block: the memory
+  //  counter is in order, so a small load that goes out last is awaited with everything else)
+  __builtin_amdgcn_sched_barrier(0);
+}
+// ... and from there to LDS, each lane what the loaders would have given it: an element beyond the mesh gets (INT32_MIN, 0)
+// for its face records, and its vertices stay unwritten
+template <class C>
+__device__ inline void stage_store(const StagedRegs<C> &r, Tab<C> &tab, double *sV, int2 *sFI, const MeshDev &m, int e0) {
+  typedef StagedRegs<C> R;
+  const int tid = threadIdx.x;
+  double *t = reinterpret_cast<double *>(&tab);
+  // The values pass through an empty asm first: without it the compiler sinks a load into the masked region of its only
+  // use, where it is followed by a wait for everything in flight -- the round trip this routine is there to remove.  With
+  // it the small loads are awaited here, once, with the nodal loads still outstanding.
+  StagedRegs<C> q = r;
+#pragma unroll
+  for (int k = 0; k < R::TR; k++) asm volatile("" : "+v"(q.t[k]));
+  asm volatile("" : "+v"(q.v), "+v"(q.f.x), "+v"(q.f.y));
+#pragma unroll
+  for (int k = 0; k < R::TR; k++)
+    if (tid + k * C::BLOCK < R::NT) t[tid + k * C::BLOCK] = q.t[k];
+  const bool inside = e0 < m.ne;
+  if (tid < R::PER && inside) sV[tid] = q.v;
+  if (tid < C::NFACES) sFI[tid] = inside ? q.f : make_int2(INT32_MIN, 0);
+}
 
 // what the closures of the 2-D heavy kernels take of the mixing-length model and the viscous sponge at one point
 // (`park`: the block's LDS array of sponge weights, one word per lane -- see EddyCtx::vsw)
@@ -597,6 +618,8 @@ __device__ inline double lift_pair(const double *Lf, const Tab<C> &tab, int le, 
 
 template <class C>
 __device__ inline void load_tables(Tab<C> &t, const Tables1D &src) {
+  // (the body of tab_image.hpp::tab_lane_copy, which the host test of the image runs lane by lane -- written out here: a call,
+  //  though inlined, moved the register allocation of eleven 2-D p = 1 k_flux kernels)
   const int tid = threadIdx.x;
   if (tid < C::N1) {
     t.x[tid] = src.x[tid];
@@ -2081,16 +2104,28 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && PH::HEAVY) ? 1 : PH::minw_grad(
   const bool node_on = tid < C::NODES && (e0 + tid / C::NPE) < m.ne;
   const int le_n = tid / C::NPE, nd = tid - le_n * C::NPE;
   int idx[3] = {nd % C::N1, (nd / C::N1) % C::N1, nd / (C::N1 * C::N1)};
-  // the state goes out first: its latency overlaps that of the tables, vertices and face records
+  constexpr bool STAGED = staged_prologue<C, PH, SWEEP_GRADIENT>();
   double u[NEQ];
-  if (node_on) {
-    const unsigned n = static_cast<unsigned>(e0 + le_n) * C::NPE + nd;
+  if constexpr (STAGED) {
+    StagedRegs<C> staged;
+    // tables, vertices and face records go out first and the state behind them, none of them under a lane mask (a node that
+    // is off reads the mesh's last element and drops it): the LDS writes below wait for the small loads alone
+    stage_issue<C>(staged, m, e0);
+    const unsigned n = static_cast<unsigned>(min(e0 + le_n, m.ne - 1)) * C::NPE + nd;
 #pragma unroll
     for (int eq = 0; eq < NEQ; eq++) u[eq] = field_ptr(U, eq, m.ndofs)[n];
+    stage_store<C>(staged, tab, sV, sFI, m, e0);
+  } else {
+    // the state goes out first: its latency overlaps that of the tables, vertices and face records
+    if (node_on) {
+      const unsigned n = static_cast<unsigned>(e0 + le_n) * C::NPE + nd;
+#pragma unroll
+      for (int eq = 0; eq < NEQ; eq++) u[eq] = field_ptr(U, eq, m.ndofs)[n];
+    }
+    load_face_info<C>(sFI, m, e0);
+    load_tables<C>(tab, ct);
+    load_vertices<C>(sV, m, e0);
   }
-  load_face_info<C>(sFI, m, e0);
-  load_tables<C>(tab, ct);
-  load_vertices<C>(sV, m, e0);
   block_sync<C::BLOCK>();
   STAMP(0);
   // neighbour Up traces of all direction pairs: issued first, consumed by the jump passes
@@ -2882,19 +2917,31 @@ __global__ __launch_bounds__(C::BLOCK, (C::NC && (PH::HEAVY || PH::MINW_FLUX > 2
   const bool node_on = tid < C::NODES && (e0 + tid / C::NPE) < m.ne;
   const int le_n = tid / C::NPE, nd = tid - le_n * C::NPE;
   int idx[3] = {nd % C::N1, (nd / C::N1) % C::N1, nd / (C::N1 * C::N1)};
-  // the nodal loads go out first: their latency (a full trip to HBM under load) then overlaps that of the
-  // tables, vertices and face records instead of following it
+  constexpr bool STAGED = staged_prologue<C, PH, SWEEP_FLUX>();
   double u[NEQ], gr[NEQ * DIM];
-  if (node_on) {
-    const unsigned n = static_cast<unsigned>(e0 + le_n) * C::NPE + nd;
+  if constexpr (STAGED) {  // (as in k_gradient: the small loads, then the nodal ones, all of them unmasked)
+    StagedRegs<C> staged;
+    stage_issue<C>(staged, m, e0);
+    const unsigned n = static_cast<unsigned>(min(e0 + le_n, m.ne - 1)) * C::NPE + nd;
 #pragma unroll
     for (int eq = 0; eq < NEQ; eq++) u[eq] = field_ptr(U, eq, m.ndofs)[n];
 #pragma unroll
     for (int k = 0; k < NEQ * DIM; k++) gr[k] = field_ptr(gradUp, k, m.ndofs)[n];
+    stage_store<C>(staged, tab, sV, sFI, m, e0);
+  } else {
+    // the nodal loads go out first: their latency (a full trip to HBM under load) then overlaps that of the
+    // tables, vertices and face records instead of following it
+    if (node_on) {
+      const unsigned n = static_cast<unsigned>(e0 + le_n) * C::NPE + nd;
+#pragma unroll
+      for (int eq = 0; eq < NEQ; eq++) u[eq] = field_ptr(U, eq, m.ndofs)[n];
+#pragma unroll
+      for (int k = 0; k < NEQ * DIM; k++) gr[k] = field_ptr(gradUp, k, m.ndofs)[n];
+    }
+    load_face_info<C>(sFI, m, e0);
+    load_tables<C>(tab, ct);
+    load_vertices<C>(sV, m, e0);
   }
-  load_face_info<C>(sFI, m, e0);
-  load_tables<C>(tab, ct);
-  load_vertices<C>(sV, m, e0);
   block_sync<C::BLOCK>();
   FSTAMP(0);
   NbTraces<C, NEQ> ta0;

@@ -221,6 +221,11 @@ inline void upload_tables(int dim, int order, int nc = 0) {
   const Tables1D tabs = make_tables(order, dim, nc, nc);
   const size_t off = ((static_cast<size_t>(nc) * 2 + (dim - 2)) * (TPSRHS_MAXORDER + 1) + order) * sizeof(Tables1D);
   HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_tab), &tabs, sizeof(Tables1D), off, hipMemcpyHostToDevice));
+  // ... and the packed image that the kernels with the staged prologue copy to LDS as it stands (kernels.hpp::stage_issue)
+  if (dim == StagedCfg::DIM && order == StagedCfg::P && nc == StagedCfg::NC) {
+    const Tab<StagedCfg> image = make_tab_image<StagedCfg>(tabs);
+    HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_tab_image), &image, sizeof(image), 0, hipMemcpyHostToDevice));
+  }
 }
 
 // non-collocated (Gauss-Lobatto / Gauss-Lobatto) kernels: orders 1..3
