@@ -850,6 +850,28 @@ int tpsrhs_visualization_fields(tpsrhs_handle h, const double *x, double *out);
  * two-temperature mixture, to the electron-energy equation.  NULL disables the term. */
 int tpsrhs_set_joule_heating(tpsrhs_handle h, const double *joule_heating);
 
+/* ---- the flow side of the coupling to an electron Boltzmann solver (src/M2ulPhyS2Boltzmann.cpp) -------------------------
+ * A reaction with reaction_models[r] = TPSRHS_GRIDFUNCTION_RXN (reactions/reactionN/model = bte) is the reference's
+ * GridFunctionReaction (src/reaction.cpp:85-117, src/chemistry.cpp:89-91,133-139): its forward rate coefficient is read per
+ * node from one component of a rate array.  The component -- bte/index, ReactionInput::indexInput -- is passed in
+ * rate_params[0 + r * TPSRHS_MAXCHEMPARAMS]; a value that is not an integer >= 0: TPSRHS_ERR_INVALID_ARGUMENT at
+ * tpsrhs_create.  Stoichiometry, reaction energy, detailed balance and the equilibrium constant are as for every reaction.
+ *
+ * M2ulPhyS::fetch (:89-101).  `rates` is a DEVICE array [num_components][size], byNODES, owned by the caller and read at every
+ * Mult (like the array of tpsrhs_set_joule_heating; the kinetic solver refreshes it between steps).  Component c starts at
+ * rates + c * size, as GridFunctionReaction::setGridFunction has it -- NOT as setData has it, which offsets by the size of
+ * the PREVIOUS call (src/reaction.cpp:90-93).  NULL removes the array: an external reaction then has k_f = 0, as the
+ * reference returns when data_ is null.  size != NDofs, num_components not greater than every configured component, or a
+ * non-NULL array on an operator without such a reaction: TPSRHS_ERR_INVALID_ARGUMENT.  While an array is set the RK4 stages
+ * take the unfused path, as with a forcing term.  A time-loop graph captured before the call is not replayed after it. */
+int tpsrhs_set_reaction_rates(tpsrhs_handle h, const double *rates, int num_components, int64_t size);
+/* M2ulPhyS::push (:40-87): what the Boltzmann solver gets.  x: DEVICE, the layout of tpsrhs_mult.  out: DEVICE
+ * [num_species + 2][NDofs] -- rows 0 .. num_species-1 hold AVOGADRONUMBER * n_sp of computeNumberDensities of the UNCLAMPED
+ * state (particles per m^3), then the heavy and the electron temperature of computeTemperaturesBase (the two rows are equal
+ * for a one-temperature mixture).  1 <= num_species <= the mixture's species count, else TPSRHS_ERR_INVALID_ARGUMENT.
+ * Asynchronous on the operator's stream.  Dry air and the table gas: TPSRHS_ERR_UNSUPPORTED. */
+int tpsrhs_boltzmann_fields(tpsrhs_handle h, const double *x, int num_species, double *out);
+
 /* Host-only view of the face topology tpsrhs_create derives from a mesh (the role of the
  * indirection arrays of src/M2ulPhyS.cpp:816-1486); touches no device.  Outputs (caller-allocated):
  *   face_nbr[ne*2*dim]   >= 0: trace slot (element*2*dim + local face) of the neighbour, slots

@@ -173,6 +173,19 @@ class RHSoperatorHIP : public mfem::TimeDependentOperator {
   void setMixingLength(const mfem::Vector *distance, const tpsrhs_mixing_length &prm) {
     check(tpsrhs_set_mixing_length(h_, distance ? distance->Read() : nullptr, &prm));
   }
+  // The flow side of the Boltzmann coupling (src/M2ulPhyS2Boltzmann.cpp).  push (:40-87): `fields` takes
+  // [num_species + 2][NDofs] -- AVOGADRONUMBER n_sp, then T_h and T_e -- of the state x, what the reference writes into the
+  // interface's species, heavyTemperature and electronTemperature grid functions.  fetch (:89-101): `rates` is the
+  // externalReactionRates grid function, [num_components][NDofs] byNODES, a device array owned by the caller and read at
+  // every Mult; NULL removes it.
+  void pushBoltzmannFields(const mfem::Vector &x, int num_species, mfem::Vector &fields) const {
+    check(tpsrhs_boltzmann_fields(h_, x.Read(), num_species, fields.Write()));
+  }
+  void fetchReactionRates(const mfem::Vector *rates, int num_components) {
+    const int64_t ndofs = tpsrhs_num_dofs(h_);
+    check(tpsrhs_set_reaction_rates(h_, rates ? rates->Read() : nullptr, rates ? num_components : 0,
+                                    (rates && num_components > 0) ? static_cast<int64_t>(rates->Size()) / num_components : ndofs));
+  }
   tpsrhs_handle handle() const { return h_; }
   int num_equation() const { return tpsrhs_num_equation(h_); }
 

@@ -17,6 +17,9 @@ def _code_object(obj, tmp):
                         f"--output={co}"], capture_output=True, text=True)
     if r.returncode != 0 or not os.path.exists(co) or os.path.getsize(co) == 0:
         fb = co + ".fatbin"  # the device code sits in the .hip_fatbin section of the host object
+        sections = subprocess.run([f"{LLVM}/llvm-readelf", "-S", obj], capture_output=True, text=True).stdout
+        if ".hip_fatbin" not in sections:  # a unit of host code only (external_rates.hip): no kernel to count
+            return None
         subprocess.run([f"{LLVM}/llvm-objcopy", "--dump-section", f".hip_fatbin={fb}", obj, co + ".discard.o"], check=True)  # (an explicit output: with one file name llvm-objcopy rewrites its INPUT in place -- and bumps the mtime the build compares)
         subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--targets={TARGET}", f"--input={fb}",
                         f"--output={co}"], check=True)
@@ -36,8 +39,10 @@ def census(objdir=OBJ):
         for o in sorted(os.listdir(objdir)):
             if not o.endswith(".o"):
                 continue
-            notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", _code_object(os.path.join(objdir, o), tmp)],
-                                   capture_output=True, text=True).stdout
+            co = _code_object(os.path.join(objdir, o), tmp)
+            if co is None:
+                continue
+            notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
             names = []
             for blk in notes.split("- .agpr_count")[1:]:
                 name = re.search(r"\.name:\s+(\S+)", blk).group(1)

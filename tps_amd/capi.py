@@ -23,6 +23,7 @@ EULER, NS, NS_PASSIVE = 0, 1, 2
 DRY_AIR, USER_DEFINED, LTE_FLUID = 0, 1, 2
 ARGON_MINIMAL, ARGON_MIXTURE, CONSTANT = 0, 1, 2
 ARRHENIUS, HOFFERTLIEN, TABULATED_RXN = 0, 1, 2
+GRIDFUNCTION_RXN, RADIATIVE_DECAY = 3, 4  # model = bte (RHSoperator.setReactionRates); 4 is not built
 NONE_RAD, NET_EMISSION = 0, 1
 SPECIES_MW, SPECIES_CHARGES, FORMATION_ENERGY, SPECIES_DEGENERACY = 0, 1, 2, 3
 CLMB_ATT, CLMB_REP, AR_AR1P, AR_E, AR_AR, NONE_ARGCOLL = 0, 1, 2, 3, 4, 5
@@ -686,6 +687,8 @@ def load():
     lib.tpsrhs_set_dt.argtypes = [vp, C.c_double]
     lib.tpsrhs_set_forcing.argtypes = [vp, C.POINTER(Forcing)]
     lib.tpsrhs_set_joule_heating.argtypes = [vp, C.c_void_p]
+    lib.tpsrhs_set_reaction_rates.argtypes = [vp, C.c_void_p, C.c_int, C.c_int64]
+    lib.tpsrhs_boltzmann_fields.argtypes = [vp, vp, C.c_int, vp]
     lib.tpsrhs_set_mixing_length.argtypes = [vp, C.c_void_p, C.POINTER(MixingLength)]
     lib.tpsrhs_face_tables.restype = C.c_int
     lib.tpsrhs_face_tables.argtypes = [C.POINTER(Mesh), C.c_int, C.POINTER(BC), vp, vp, vp, vp]
@@ -712,6 +715,7 @@ EXPORTED_SYMBOLS = [
     "tpsrhs_wall_faces", "tpsrhs_wall_distance",
     "tpsrhs_quadrature_points", "tpsrhs_integrate", "tpsrhs_nodal_stats", "tpsrhs_monitor_configure", "tpsrhs_monitor_read",
     "tpsrhs_visualization_layout", "tpsrhs_visualization_fields",
+    "tpsrhs_set_reaction_rates", "tpsrhs_boltzmann_fields",
 ]
 
 

@@ -19,6 +19,9 @@ struct TableDev;  // physics_plasma.hpp
 tpsrhs::TableDev upload_table(std::vector<DevBuf<void>> &owner, const tpsrhs_table &t);
 // the polynomial table of the Coulomb fits (coulomb_table.hpp), filled once per process from the literals of the closure
 const std::vector<double> &coulomb_table_host();
+// the per-node passes of a plasma operator's family (plasma_vis_family.hpp: tpsrhs_visualization_fields, and
+// external_rates.hip), loaded on demand; `who` starts the message of a refusal
+void load_plasma_vis_family(tpsrhs_operator *h, const char *who);
 
 // ---- the observers of the device time loop (time_loop.hip: after_step / work_due_after_next).  The loop knows each by its
 // StepCadence (record_log.hpp; NULL: not configured, interval 0: off) and by the function that does its work on the

@@ -118,7 +118,7 @@ void launch_all(tpsrhs_operator *op, const double *x, double *y, bool gradients_
   };
   // ConstantPressureGradient / SpongeZone / HeatSource / JouleHeating, after the last k_flux launch
   auto forcing = [&](const MeshDev &m) {
-    if (!op->forcing_active) return;
+    if (!op->forcing_terms) return;
     if constexpr (PH::HAS_MIXED_OUT) {  // SpongeZone::updateTerms: computeMixedOutValues first (src/forcing_terms.cpp:631-635)
       for (int z = 0; z < op->forcing.nsponge; z++) {
         if (!op->forcing.sponge[z].mixed_out) continue;
@@ -196,6 +196,9 @@ void launch_all(tpsrhs_operator *op, const double *x, double *y, bool gradients_
     flux(mh, nh);
   }
   forcing(all);
+  // the reactions with an external rate coefficient (tpsrhs_set_reaction_rates): y += their sources, a streaming pass of its
+  // own from the family's post-processing unit (external_rates.hpp); the sweeps above saw the other reactions only
+  if (op->ext.rates) op->ext_reactions(op, x, y);
   if constexpr (PH::HAS_NR_BC) {
     if (op->n_nr_faces > 0) {  // the updated states are what the next Mult's Riemann solver sees
       op->bstate_cur = 1 - op->bstate_cur;

@@ -112,7 +112,18 @@ struct tpsrhs_operator {
   MixLenDev mixlen = {nullptr, 0.0, 1.0, 0.0};  // MixingLengthTransport (tpsrhs_set_mixing_length); distance NULL: off
   ForcingDev forcing = {};                  // host copy of the optional forcing terms (tpsrhs_set_forcing / _joule_heating)
   DevBuf<ForcingDev> d_forcing;
-  bool forcing_active = false;
+  bool forcing_terms = false;   // some term of `forcing` is set: k_forcing runs after the last k_flux launch
+  bool forcing_active = false;  // forcing_terms, or reaction rates are set (ext.rates): some pass adds to the residual in memory
+  // Reactions whose forward rate coefficient comes from outside (TPSRHS_GRIDFUNCTION_RXN; GridFunctionReaction,
+  // src/reaction.cpp:85-117): the second chemistry block, which holds them alone (plasma_params_host.hpp::split_chemistry;
+  // d_chem above holds the others), and the caller's rate array of tpsrhs_set_reaction_rates
+  struct ExternalRates {
+    DevBuf<void> d_chem;            // ChemDev of the external reactions; empty: the operator has none
+    int num_reactions = 0;
+    int num_components_needed = 0;  // 1 + the largest component index a reaction reads
+    const double *rates = nullptr;  // [num_components][ndofs], the caller's; NULL: k_f = 0, no pass
+    int num_components = 0;
+  } ext;
   // non-reflecting inlet / outlet patches (dry air): their faces {slot, bc index}, slot -> ordinal, the
   // double-buffered boundary state, the patch sums of the primitives, the time step they integrate with
   bool has_nr = false;  // some boundary condition is of a non-reflecting type (possibly without local faces)
@@ -165,6 +176,10 @@ struct tpsrhs_operator {
   // tpsrhs_visualization_fields: the post-processing passes of the plasma families (visualization.hpp); NULL for every other
   // physics
   void (*vis_fields)(tpsrhs_operator *, const VisRows &, const double *, double *) = nullptr;
+  // external_rates.hpp, set with vis_fields from the same shared object: the pass of the external reactions (y += their
+  // sources, after the last k_flux launch of a Mult: launch.hpp) and tpsrhs_boltzmann_fields
+  void (*ext_reactions)(tpsrhs_operator *, const double *, double *) = nullptr;
+  void (*boltzmann_fields)(tpsrhs_operator *, const double *, int, double *) = nullptr;
   // tpsrhs_stats_configure / tpsrhs_sampler_create, tpsrhs_probe_configure / tpsrhs_integrate, tpsrhs_monitor_configure;
   // NULL: none yet.  Last, and reset first in the destructor: they go while the events and the second stream still exist.
   // Whoever lets one go while its kernels may still run synchronises the stream first (tpsrhs_destroy, the configure calls).

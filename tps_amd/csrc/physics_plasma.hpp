@@ -2075,6 +2075,58 @@ struct PlasmaPhys {
       store(r, kf * rate);
     }
   }
+
+  // ---- reactions whose forward rate coefficient comes from outside (external_rates.hpp) ----------------------------------
+  // GridFunctionReaction (src/reaction.cpp:85-117, model = bte): k_f of reaction r is read per node from component
+  // c.rate[0 + r * 3] of a rate array, through `kf_of(component)`; the rest is the rate loop of `source` for the reactions
+  // of the block `c` -- the SECOND chemistry block of the operator, which holds the external reactions alone
+  // (plasma_params_host.hpp::split_chemistry).  The same clamps, the same temperatures (from Up, limited by
+  // min_temperature), the same number densities as `source`; out come the species' creation rates [NSP] and the electron
+  // energy loss, which the caller adds to the residual (sources add up over the reactions).  A new closure: `source` and
+  // `progress_rates` stay token for token.  (CD: the block through the generic or the CONSTANT address space.)
+  template <class CD, class KF>
+  __device__ static inline void external_source(PRef p, const CD &c, const double *Uin, const double *Upin, KF &&kf_of,
+                                                double *creation, double &e_loss) {
+    double U[NEQ], Up[NEQ];
+#pragma unroll
+    for (int eq = 0; eq < NEQ; eq++) {
+      U[eq] = Uin[eq];
+      Up[eq] = Upin[eq];
+    }
+#pragma unroll
+    for (int sp = 0; sp < NACTIVE; sp++) {
+      const int eq = 3 + 2 + sp;  // as in `source`: nvel = 3 of src/source_term.cpp:129
+      if (eq < NEQ) {
+        U[eq] = fmax(U[eq], 0.0);
+        Up[eq] = fmax(Up[eq], 0.0);
+      }
+    }
+    const double Th = Up[ITH], Te = TWOT ? Up[ITE] : Up[ITH];
+    const Species q = species(p, U);
+    const double Thl = fmax(Th, c.min_temperature), Tel = fmax(Te, c.min_temperature);
+    e_loss = 0.0;
+#pragma unroll
+    for (int sp = 0; sp < NSP; sp++) creation[sp] = 0.0;
+    for (int r = 0; r < c.num_reactions; r++) {
+      const bool el = (c.electron_index < 0) ? false : (c.reactant[c.electron_index + r * NSP] != 0);
+      const double temp = el ? Tel : Thl;
+      const double kf = kf_of(static_cast<int>(c.rate[0 + r * 3]));
+      double rate = 1.0;
+#pragma unroll
+      for (int sp = 0; sp < NSP; sp++) rate *= ipow(q.n[sp], c.reactant[sp + r * NSP]);
+      if (c.detailed_balance[r]) {
+        const double kc = c.keq[0 + r * 3] * fexp(c.keq[1 + r * 3] * flog(temp) - c.keq[2 + r * 3] / temp);
+        double bwd = 1.0;
+#pragma unroll
+        for (int sp = 0; sp < NSP; sp++) bwd *= ipow(q.n[sp], c.product[sp + r * NSP]);
+        rate -= bwd / kc;
+      }
+      const double progress = kf * rate;
+      if (TWOT && el) e_loss += c.energy[r] * progress;
+#pragma unroll
+      for (int sp = 0; sp < NSP; sp++) creation[sp] += progress * (c.product[sp + r * NSP] - c.reactant[sp + r * NSP]);
+    }
+  }
 };
 
 }  // namespace tpsrhs

@@ -5,6 +5,7 @@
 #ifndef TPSRHS_PLASMA_PARAMS_HOST_HPP_
 #define TPSRHS_PLASMA_PARAMS_HOST_HPP_
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <stdexcept>
@@ -52,11 +53,85 @@ inline TableDev table_coeffs(const tpsrhs_table &t, std::vector<double> &buf) {
 }
 
 
-// `place_table(const tpsrhs_table &) -> TableDev` gives a table's coefficients a home (the library: a device buffer) and
-// returns the record that points there.  p.chem is left for the caller (the library uploads `c` and stores its address).
+// Chemistry::Chemistry (src/chemistry.cpp:38-147) in TWO blocks.  `sweep` is what the sweeps and every kernel of the create
+// path see: the reactions with a closed form (Arrhenius, Hoffert-Lien, tabulated), compacted, in their order, with
+// table_share counted in the compacted numbering.  `ext` holds the reactions whose forward rate coefficient comes from
+// outside (TPSRHS_GRIDFUNCTION_RXN; GridFunctionReaction, src/reaction.cpp:85-117, src/chemistry.cpp:89-91,133-139):
+// stoichiometry, energy, detailed-balance flag and keq as for the others, and in rate[0 + r * TPSRHS_MAXCHEMPARAMS] the
+// component of the rate array the reaction reads -- the reference's ReactionInput::indexInput, which the caller passes in
+// the same slot of rate_params (modelParams, tableInput and indexInput sit side by side there too).  With no external
+// reaction `sweep` is what this function filled before there was a second block, and ext.num_reactions is 0.
+// `place_table(const tpsrhs_table &) -> TableDev` gives a table's coefficients a home (the library: a device buffer).
 template <int NSP, class PlaceTable>
-void fill_plasma_params(PlasmaParams<NSP> &p, ChemDev &chem, const tpsrhs_disc *disc, const tpsrhs_physics *phys, int num_bcs,
-                        const tpsrhs_bc *bcs, PlaceTable &&place_table) {
+void split_chemistry(const tpsrhs_chemistry &ch, ChemDev &sweep, ChemDev &ext, PlaceTable &&place_table) {
+  if (ch.num_reactions < 0 || ch.num_reactions > TPSRHS_MAXREACTIONS) throw std::invalid_argument("num_reactions");
+  std::memset(static_cast<void *>(&sweep), 0, sizeof(ChemDev));
+  std::memset(static_cast<void *>(&ext), 0, sizeof(ChemDev));
+  for (ChemDev *c : {&sweep, &ext}) {
+    c->electron_index = ch.electron_index;
+    c->min_temperature = ch.minimum_temperature;
+  }
+  int origin[TPSRHS_MAXREACTIONS] = {0};  // reaction of `ch` behind reaction q of `sweep`
+  for (int r = 0; r < ch.num_reactions; r++) {
+    const int model = ch.reaction_models[r];
+    if (model == TPSRHS_RADIATIVE_DECAY || model > TPSRHS_RADIATIVE_DECAY || model < 0)
+      throw UnsupportedConfig("reaction model outside the built scope (Arrhenius, Hoffert-Lien, tabulated, grid function)");
+    const bool external = (model == TPSRHS_GRIDFUNCTION_RXN);
+    ChemDev *c = external ? &ext : &sweep;
+    const int q = c->num_reactions++;
+    c->energy[q] = ch.reaction_energies[r];
+    c->model[q] = static_cast<signed char>(model);
+    c->detailed_balance[q] = ch.detailed_balance[r] != 0;
+    for (int k = 0; k < TPSRHS_MAXCHEMPARAMS; k++) {
+      c->rate[k + q * TPSRHS_MAXCHEMPARAMS] = ch.rate_params[k + r * TPSRHS_MAXCHEMPARAMS];
+      c->keq[k + q * TPSRHS_MAXCHEMPARAMS] = ch.equilibrium_constant_params[k + r * TPSRHS_MAXCHEMPARAMS];
+    }
+    for (int sp = 0; sp < NSP; sp++) {
+      const int a = ch.reactant_stoich[sp + r * NSP], b = ch.product_stoich[sp + r * NSP];
+      if (a < 0 || a > 8 || b < 0 || b > 8) throw std::invalid_argument("stoichiometric coefficient out of range");
+      c->reactant[sp + q * NSP] = static_cast<signed char>(a);
+      c->product[sp + q * NSP] = static_cast<signed char>(b);
+    }
+    c->table_share[q] = static_cast<signed char>(q);
+    if (external) {
+      // bte/index: a component of the rate array, so an integer >= 0 (how many the array has is known when it is set)
+      const double comp = ch.rate_params[0 + r * TPSRHS_MAXCHEMPARAMS];
+      if (!(comp >= 0.0) || comp != std::floor(comp) || comp >= 2147483647.0)
+        throw std::invalid_argument("grid-function reaction: rate_params[0] must hold the component index (an integer >= 0)");
+      for (int k = 1; k < TPSRHS_MAXCHEMPARAMS; k++) c->rate[k + q * TPSRHS_MAXCHEMPARAMS] = 0.0;
+      continue;
+    }
+    origin[q] = r;
+    if (model == TPSRHS_TABULATED_RXN) {
+      c->table[q] = place_table(ch.rate_tables[r]);
+      const tpsrhs_table &t = ch.rate_tables[r];
+      for (int o = 0; o < q; o++) {  // an earlier tabulated reaction on the same abscissae (same scale flag: the same search)?
+        if (c->model[o] != TPSRHS_TABULATED_RXN || c->table_share[o] != o) continue;
+        const tpsrhs_table &ot = ch.rate_tables[origin[o]];
+        if (ot.n_data != t.n_data) continue;
+        bool same = true;
+        for (int k = 0; k < t.n_data && same; k++) same = (ot.x_data[k] == t.x_data[k]);
+        if (same) {
+          c->table_share[q] = static_cast<signed char>(o);
+          break;
+        }
+      }
+    }
+  }
+}
+
+// 1 + the largest component index a reaction of `ext` reads (0: no external reaction)
+inline int external_components_needed(const ChemDev &ext) {
+  int need = 0;
+  for (int r = 0; r < ext.num_reactions; r++) need = std::max(need, 1 + static_cast<int>(ext.rate[0 + r * TPSRHS_MAXCHEMPARAMS]));
+  return need;
+}
+
+// p.chem is left for the caller (the library uploads `chem` and stores its address).  `chem` is the block of the sweeps,
+// `ext` that of the reactions with an external rate coefficient (split_chemistry above); radiation goes with the first.
+template <int NSP, class PlaceTable>
+void fill_plasma_params(PlasmaParams<NSP> &p, ChemDev &chem, ChemDev &ext, const tpsrhs_disc *disc, const tpsrhs_physics *phys,
+                        int num_bcs, const tpsrhs_bc *bcs, PlaceTable &&place_table) {
   const tpsrhs_perfect_mixture &mx = phys->mixture;
   std::memset(static_cast<void *>(&p), 0, sizeof(p));
   for (int sp = 0; sp < NSP; sp++) {
@@ -149,48 +224,19 @@ void fill_plasma_params(PlasmaParams<NSP> &p, ChemDev &chem, const tpsrhs_disc *
     for (int k = 0; k < 4 + TPSRHS_MAXSPECIES; k++) p.bc[i].data[k] = bcs[i].data[k];
   }
   // chemistry + radiation block
-  const tpsrhs_chemistry &ch = phys->chemistry;
-  if (ch.num_reactions < 0 || ch.num_reactions > TPSRHS_MAXREACTIONS) throw std::invalid_argument("num_reactions");
   ChemDev *c = &chem;
-  std::memset(static_cast<void *>(c), 0, sizeof(ChemDev));
-  c->num_reactions = ch.num_reactions;
-  c->electron_index = ch.electron_index;
-  c->min_temperature = ch.minimum_temperature;
-  for (int r = 0; r < ch.num_reactions; r++) {
-    c->energy[r] = ch.reaction_energies[r];
-    c->model[r] = static_cast<signed char>(ch.reaction_models[r]);
-    c->detailed_balance[r] = ch.detailed_balance[r] != 0;
-    if (ch.reaction_models[r] > TPSRHS_TABULATED_RXN || ch.reaction_models[r] < 0)
-      throw UnsupportedConfig("reaction model outside the built scope (Arrhenius, Hoffert-Lien, tabulated)");
-    for (int k = 0; k < TPSRHS_MAXCHEMPARAMS; k++) {
-      c->rate[k + r * TPSRHS_MAXCHEMPARAMS] = ch.rate_params[k + r * TPSRHS_MAXCHEMPARAMS];
-      c->keq[k + r * TPSRHS_MAXCHEMPARAMS] = ch.equilibrium_constant_params[k + r * TPSRHS_MAXCHEMPARAMS];
-    }
-    for (int sp = 0; sp < NSP; sp++) {
-      const int a = ch.reactant_stoich[sp + r * NSP], b = ch.product_stoich[sp + r * NSP];
-      if (a < 0 || a > 8 || b < 0 || b > 8) throw std::invalid_argument("stoichiometric coefficient out of range");
-      c->reactant[sp + r * NSP] = static_cast<signed char>(a);
-      c->product[sp + r * NSP] = static_cast<signed char>(b);
-    }
-    c->table_share[r] = static_cast<signed char>(r);
-    if (ch.reaction_models[r] == TPSRHS_TABULATED_RXN) {
-      c->table[r] = place_table(ch.rate_tables[r]);
-      const tpsrhs_table &t = ch.rate_tables[r];
-      for (int q = 0; q < r; q++) {  // an earlier tabulated reaction on the same abscissae (same scale flag: the same search)?
-        if (ch.reaction_models[q] != TPSRHS_TABULATED_RXN || c->table_share[q] != q) continue;
-        const tpsrhs_table &o = ch.rate_tables[q];
-        if (o.n_data != t.n_data) continue;
-        bool same = true;
-        for (int k = 0; k < t.n_data && same; k++) same = (o.x_data[k] == t.x_data[k]);
-        if (same) {
-          c->table_share[r] = static_cast<signed char>(q);
-          break;
-        }
-      }
-    }
-  }
+  split_chemistry<NSP>(phys->chemistry, chem, ext, place_table);
   c->radiation = phys->radiation.model;
   if (c->radiation == TPSRHS_NET_EMISSION) c->nec = place_table(phys->radiation.nec_table);
+}
+
+// ... for the callers that build one block (the host builds of the point physics): a chemistry without external reactions
+template <int NSP, class PlaceTable>
+void fill_plasma_params(PlasmaParams<NSP> &p, ChemDev &chem, const tpsrhs_disc *disc, const tpsrhs_physics *phys, int num_bcs,
+                        const tpsrhs_bc *bcs, PlaceTable &&place_table) {
+  ChemDev ext;
+  fill_plasma_params<NSP>(p, chem, ext, disc, phys, num_bcs, bcs, place_table);
+  if (ext.num_reactions > 0) throw UnsupportedConfig("grid-function reactions need the second chemistry block");
 }
 
 }  // namespace tpsrhs

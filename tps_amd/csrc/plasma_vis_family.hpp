@@ -1,4 +1,4 @@
-// The post-processing passes (visualization.hpp, k_vis_fields) of the plasma kernel families, in translation units of
+// The post-processing passes (visualization.hpp, k_vis_fields; external_rates.hpp) of the plasma kernel families, in translation units of
 // their own: plasma_vis_<geo>_n<species>[a].hip -> libtpsrhs_plasma_vis_<...>.so, loaded by the core at the first
 // tpsrhs_visualization_fields of an operator of that family (tpsrhs.hip::load_family), one per (geometry, species count,
 // ambipolar or not) -- the passes do not depend on the polynomial order.
@@ -11,12 +11,16 @@
 #ifndef TPSRHS_PLASMA_VIS_FAMILY_HPP_
 #define TPSRHS_PLASMA_VIS_FAMILY_HPP_
 
+#include "external_rates.hpp"
 #include "launch.hpp"
 #include "physics_plasma.hpp"
 
 template <int DIM, int NVEL, int NSP, bool AMBI, bool TWOT, int TR>
 static void pick_plasma_vis_of(tpsrhs_operator *op) {
   op->vis_fields = &launch_vis_fields<PlasmaPhys<DIM, NVEL, NSP, AMBI, TWOT, TR>>;
+  // the per-node passes of the Boltzmann coupling (external_rates.hpp) need the same closures and live here for the same reason
+  op->ext_reactions = &launch_external_reactions<PlasmaPhys<DIM, NVEL, NSP, AMBI, TWOT, TR>>;
+  op->boltzmann_fields = &launch_boltzmann_fields<PlasmaPhys<DIM, NVEL, NSP, AMBI, TWOT, TR>>;
 }
 
 // the transport models a family instantiates: those of plasma_family.hpp::pick_plasma_family

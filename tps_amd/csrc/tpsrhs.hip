@@ -7,7 +7,7 @@
 // This unit: the family loader, the parameter blocks and setup, create / destroy / mult, the setters and getters, timing,
 // statuses, the two visualization entries, and the planar dry-air instantiations of the sweeps.  The other features of
 // the C ABI have units of their own -- time_loop.hip, statistics.hip, sampling.hip, integrals.hip, wall_distance.hip,
-// probes.hip -- and share abi_support.hpp with this one.
+// probes.hip, external_rates.hip -- and share abi_support.hpp with this one.
 #include "abi_support.hpp"
 #include "element_geometry.hpp"
 #include "launch.hpp"
@@ -115,15 +115,23 @@ void fill_plasma_params(tpsrhs_operator *op, const tpsrhs_disc *disc, const tpsr
                         const tpsrhs_bc *bcs) {
   static_assert(sizeof(PlasmaParams<NSP>) <= sizeof(op->params), "parameter block too large");
   PlasmaParams<NSP> &p = *new (op->params) PlasmaParams<NSP>;
-  std::unique_ptr<ChemDev> c(new ChemDev);
+  std::unique_ptr<ChemDev> c(new ChemDev), ext(new ChemDev);
   try {
-    tpsrhs::fill_plasma_params<NSP>(p, *c, disc, phys, num_bcs, bcs, [op](const tpsrhs_table &t) { return upload_table(op->d_extra, t); });
+    tpsrhs::fill_plasma_params<NSP>(p, *c, *ext, disc, phys, num_bcs, bcs, [op](const tpsrhs_table &t) { return upload_table(op->d_extra, t); });
   } catch (const UnsupportedConfig &e) {  // (its header is also built alone, on the host, by tests/host_physics: it keeps its own type)
     throw Unsupported(e.what());
   }
   op->d_chem = DevBuf<ChemDev>(1);
   p.chem = static_cast<ChemDev *>(op->d_chem.get());
   HIP_CHECK(hipMemcpy(op->d_chem.get(), c.get(), sizeof(ChemDev), hipMemcpyHostToDevice));
+  // the reactions with an external rate coefficient, where there are any: a block of their own for a pass of its own
+  // (external_rates.hpp); the block above does not hold them
+  if (ext->num_reactions > 0) {
+    op->ext.d_chem = DevBuf<ChemDev>(1);
+    HIP_CHECK(hipMemcpy(op->ext.d_chem.get(), ext.get(), sizeof(ChemDev), hipMemcpyHostToDevice));
+    op->ext.num_reactions = ext->num_reactions;
+    op->ext.num_components_needed = external_components_needed(*ext);
+  }
 }
 
 // the mixture's parameter block and the kernels of its family (the plan names the shared object)
@@ -489,8 +497,9 @@ int tpsrhs_set_dt(tpsrhs_handle h, double dt) {
 namespace {
 void upload_forcing(tpsrhs_operator *h) {
   const ForcingDev &f = h->forcing;
-  h->forcing_active = f.has_pg || f.nheat > 0 || f.nsponge > 0 || f.nps > 0 || f.joule != nullptr;
-  if (!h->forcing_active) return;
+  h->forcing_terms = f.has_pg || f.nheat > 0 || f.nsponge > 0 || f.nps > 0 || f.joule != nullptr;
+  h->forcing_active = h->forcing_terms || h->ext.rates != nullptr;
+  if (!h->forcing_terms) return;
   HIP_CHECK(hipSetDevice(h->device));
   if (!h->d_forcing) h->d_forcing = DevBuf<ForcingDev>(1);
   HIP_CHECK(hipStreamSynchronize(h->stream));  // an earlier Mult may still read the block
@@ -620,13 +629,14 @@ int tpsrhs_set_forcing(tpsrhs_handle h, const tpsrhs_forcing *in) {
     // the device block first; the host copy, the buffers of the mixed-out zones and the configuration epoch are committed
     // only once it is in place -- if the upload fails the operator keeps its previous forcing and its buffers
     const ForcingDev prev = h->forcing;
-    const bool prev_active = h->forcing_active;
+    const bool prev_active = h->forcing_active, prev_terms = h->forcing_terms;
     h->forcing = f;
     {
       ScopeExit rollback([&](bool failed) {
         if (failed) {
           h->forcing = prev;
           h->forcing_active = prev_active;
+          h->forcing_terms = prev_terms;
         }
       });
       upload_forcing(h);  // synchronises the stream before it overwrites the device block
@@ -838,6 +848,21 @@ int vis_layout(const tpsrhs_physics &ph, int dim, int axisymmetric, tpsrhs_vis_l
 }
 }  // namespace
 
+// the per-node passes of the operator's family (plasma_vis_family.hpp): a shared object of its own, loaded at the first call
+// that needs one of them; sets vis_fields, ext_reactions and boltzmann_fields
+void load_plasma_vis_family(tpsrhs_operator *h, const char *who) {
+  if (h->vis_fields) return;
+  const tpsrhs_perfect_mixture &mx = h->phys.mixture;
+  const int tr = (h->phys.transport_model == TPSRHS_CONSTANT)
+                     ? TRANSPORT_CONSTANT
+                     : (h->phys.transport_model == TPSRHS_ARGON_MINIMAL ? TRANSPORT_ARGON_MINIMAL : TRANSPORT_ARGON_MIXTURE);
+  const char *geo = (h->dim == 3) ? "3d" : (h->nvel > h->dim ? "axi" : "2d");
+  const std::string unit = std::string("plasma_vis_") + geo + "_n" + std::to_string(mx.num_species) + (mx.ambipolar ? "a" : "");
+  char msg[512] = {0};
+  const int rc = load_family(unit)(h, mx.two_temperature ? 1 : 0, tr, msg, static_cast<int>(sizeof msg));
+  if (rc != TPSRHS_OK || !h->vis_fields || !h->ext_reactions || !h->boltzmann_fields) throw Unsupported(std::string(who) + ": " + msg);
+}
+
 extern "C" {
 
 int tpsrhs_visualization_layout(const tpsrhs_physics *physics, int dim, int axisymmetric, tpsrhs_vis_layout *out) {
@@ -855,17 +880,10 @@ int tpsrhs_visualization_fields(tpsrhs_handle h, const double *x, double *out) {
     if (h->mixlen.distance)
       throw Unsupported("visualization fields: a mixing length is set; the reference would evaluate MixingLengthTransport "
                         "with the wall distance and the radius here, which is not built");
-    if (!h->vis_fields) {  // the passes of this family: a shared object of its own, loaded at the first call
-      const tpsrhs_perfect_mixture &mx = h->phys.mixture;
-      const int tr = (h->phys.transport_model == TPSRHS_CONSTANT)
-                         ? TRANSPORT_CONSTANT
-                         : (h->phys.transport_model == TPSRHS_ARGON_MINIMAL ? TRANSPORT_ARGON_MINIMAL : TRANSPORT_ARGON_MIXTURE);
-      const char *geo = (h->dim == 3) ? "3d" : (h->nvel > h->dim ? "axi" : "2d");
-      const std::string unit = std::string("plasma_vis_") + geo + "_n" + std::to_string(mx.num_species) + (mx.ambipolar ? "a" : "");
-      char msg[512] = {0};
-      const int rc = load_family(unit)(h, mx.two_temperature ? 1 : 0, tr, msg, static_cast<int>(sizeof msg));
-      if (rc != TPSRHS_OK || !h->vis_fields) throw Unsupported(std::string("visualization fields: ") + msg);
-    }
+    if (h->ext.num_reactions > 0)
+      throw Unsupported("visualization fields: the operator has reactions with an external rate coefficient; the progress-rate "
+                        "rows index the full reaction list, which no kernel sees (DESIGN.md section 1)");
+    load_plasma_vis_family(h, "visualization fields");
     HIP_CHECK(hipSetDevice(h->device));
     h->launch(h, x, nullptr, true);  // rhsOperator->updateGradients(*U, false): Up and gradUp of x
     const VisRows rows = {l.Xsp, l.Ysp, l.nsp_, l.FluxTrns, l.diffVel, l.SrcTrns, l.SpeciesTrns, l.rxn};

@@ -384,6 +384,33 @@ class RHSoperator:
         if st != 0:
             raise TpsRhsError(st, "tpsrhs_set_joule_heating")
 
+    def setReactionRates(self, rates):
+        """``M2ulPhyS::fetch`` (``src/M2ulPhyS2Boltzmann.cpp:89-101``): the forward rate coefficients of the reactions with
+        ``model = bte`` (``capi.GRIDFUNCTION_RXN``), a float64 CUDA tensor ``[num_components, NDofs]`` the operator reads at
+        every ``Mult`` (kept alive here; component = the reaction's ``bte/index``), or ``None``: those reactions then have
+        ``k_f = 0``.  The shape is checked by the library (``TPSRHS_ERR_INVALID_ARGUMENT``)."""
+        if rates is not None:
+            if rates.dtype != torch.float64 or not rates.is_cuda or not rates.is_contiguous() or rates.dim() != 2:
+                raise ValueError("expected a contiguous float64 CUDA tensor [num_components, NDofs]")
+        st = self._lib.tpsrhs_set_reaction_rates(
+            self._h, C.c_void_p(rates.data_ptr()) if rates is not None else None,
+            int(rates.shape[0]) if rates is not None else 0, int(rates.shape[1]) if rates is not None else 0)
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_set_reaction_rates")
+        self._reaction_rates = rates
+
+    def boltzmannFields(self, x: torch.Tensor, num_species=None) -> torch.Tensor:
+        """``M2ulPhyS::push`` (``src/M2ulPhyS2Boltzmann.cpp:40-87``): a ``[num_species + 2, NDofs]`` device tensor -- the
+        number densities of the first ``num_species`` species in particles per m^3 (default: all of them), then the heavy and
+        the electron temperature -- at the nodes of the state ``x``.  Asynchronous on the operator's stream."""
+        self._check(x)
+        nsp = int(self._physics.mixture.num_species) if num_species is None else int(num_species)
+        out = torch.empty((max(nsp, 0) + 2, self.NDofs), dtype=torch.float64, device=self.device)
+        st = self._lib.tpsrhs_boltzmann_fields(self._h, C.c_void_p(x.data_ptr()), nsp, C.c_void_p(out.data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_boltzmann_fields")
+        return out
+
     def setMixingLength(self, distance, max_mixing_length=0.0, pr_ratio=1.0, lewis=1.0, bulk_multiplier=0.0):
         """``MixingLengthTransport`` (``src/mixing_length_transport.cpp``, ``[flow] useMixingLength``): ``distance`` =
         the wall-distance grid function, a float64 CUDA tensor of NDofs entries read at every ``Mult`` (kept alive
