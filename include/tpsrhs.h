@@ -243,7 +243,7 @@ typedef struct tpsrhs_visc_sponge { /* viscositySpongeData (src/M2ulPhyS.cpp:583
  * "T_energy_R_c" and "T_mu_kappa_sigma" datasets; linear scales).  One species, num_equation = nvel + 2; the inverse
  * table T(e) is the energy table with abscissae and values swapped, as the reference builds it (:193-200), so the
  * energies must increase with the temperature.  The two-dimensional (T, rho) tables of the reference's CPU build
- * interpolate with GSL (third party, `flow/lte/table_dim = 2`) and are not built.  The radiation sink of SourceTerm
+ * (`flow/lte/table_dim = 2`, its default) are tpsrhs_lte2d below.  The radiation sink of SourceTerm
  * (src/source_term.cpp:207-209) is tpsrhs_physics::radiation; the electric conductivity table feeds the
  * plasma-conductivity side output of SourceTerm (:196): tpsrhs_get_plasma_conductivity.  Every table must have linear
  * scales (x_log_scale = f_log_scale = 0, as the reference hard-codes): TPSRHS_ERR_INVALID_ARGUMENT otherwise.
@@ -258,6 +258,41 @@ typedef struct tpsrhs_lte { /* LteMixtureInput + the TableInputs of src/M2ulPhyS
   tpsrhs_table electric_conductivity_table; /* T -> sigma [S/m] */
 } tpsrhs_lte;
 
+/* A two-dimensional table on a tensor grid, bilinear: GslTableInterpolator2D with gsl_interp2d_bilinear
+ * (src/table.cpp:170-260).  Host pointers, copied at create.  f[j * nx + i] belongs to (x[i], y[j]), the storage of the
+ * reference (:195-207).  Both axes strictly increasing, nx >= 2, ny >= 2, finite data: TPSRHS_ERR_INVALID_ARGUMENT otherwise.
+ * Cell i holds x[i] <= x < x[i+1]; the last abscissa belongs to the last cell.  With t = (x - x_i) / dx, u = (y - y_j) / dy:
+ *   z   = (1-t)(1-u) z00 + t(1-u) z10 + (1-t)u z01 + t u z11
+ *   z_x = (-(1-u) z00 + (1-u) z10 - u z01 + u z11) / dx,   z_y likewise with t and u swapped.
+ * ONE DEPARTURE from the reference: outside the table GSL raises a domain error, which aborts the program.  This library
+ * clamps the cell index to the end cell, i.e. extrapolates linearly from it, as the reference's own one-dimensional tables do
+ * (src/table.cpp:69-72). */
+typedef struct tpsrhs_table2d {
+  int nx, ny;
+  const double *x, *y, *f;
+} tpsrhs_table2d;
+
+/* WorkingFluid::LTE_FLUID with TWO-DIMENSIONAL tables (`flow/lte/table_dim = 2`, the reference's default,
+ * src/M2ulPhyS.cpp:166, test/inputs/plasma.lte2d.ini), which the reference itself refuses on a GPU (:168-170).
+ * enabled = 0: tpsrhs_physics::lte is the gas (one-dimensional tables).  enabled = 1: these tables are, and `lte` is ignored.
+ * Same kernels, entry points and scope as the one-dimensional gas: axisymmetric formulation, Gauss-Legendre pair; anything
+ * else TPSRHS_ERR_UNSUPPORTED.  Every look-up takes the density of the state it is given.  The net-emission table of
+ * tpsrhs_physics::radiation stays one-dimensional in T.  `energy`, `gas_constant` and `sound_speed` must share their axes
+ * (nx, ny, x, y equal: the columns of one thermo file, as the reference reads them), `viscosity` and `conductivity` likewise
+ * (one transport file) -- one cell search serves the tables of a file; tables that do not: TPSRHS_ERR_UNSUPPORTED.
+ * `temperature` and `electric_conductivity` may have axes of their own.  `energy` must increase with T on every density line (the Newton
+ * iteration divides by de/dT): TPSRHS_ERR_INVALID_ARGUMENT otherwise. */
+typedef struct tpsrhs_lte2d {
+  int enabled;
+  tpsrhs_table2d energy;                /* (T, rho) -> e [J/kg]         thermo file column 3 (src/lte_mixture.cpp:48-58) */
+  tpsrhs_table2d gas_constant;          /* (T, rho) -> R [J/(kg K)]     column 6 */
+  tpsrhs_table2d sound_speed;           /* (T, rho) -> c [m/s]          column 8 */
+  tpsrhs_table2d temperature;           /* (e, rho) -> T: the e_rev_table (:60-64); only the first guess of the Newton iteration */
+  tpsrhs_table2d viscosity;             /* (T, rho) -> mu [Pa s]        (src/lte_transport_properties.cpp:38-51) */
+  tpsrhs_table2d conductivity;          /* (T, rho) -> kappa [W/(m K)] */
+  tpsrhs_table2d electric_conductivity; /* (T, rho) -> sigma [S/m] */
+} tpsrhs_lte2d;
+
 typedef struct tpsrhs_physics {
   int eq_system;        /* tpsrhs_equations */
   int working_fluid;    /* tpsrhs_working_fluid */
@@ -271,6 +306,7 @@ typedef struct tpsrhs_physics {
   tpsrhs_sgs sgs;
   tpsrhs_visc_sponge visc_sponge;
   tpsrhs_lte lte;       /* LTE_FLUID only */
+  tpsrhs_lte2d lte2d;   /* LTE_FLUID only; the last member: no offset of an earlier one depends on it */
 } tpsrhs_physics;
 
 /* ---- boundary conditions: [boundaryConditions/...] (src/M2ulPhyS.cpp:3480-3700) --------------- */
@@ -383,6 +419,9 @@ int tpsrhs_eval_pointwise(tpsrhs_handle h, int quantity, int64_t n, const double
 /* TableInterpolator::eval of a LinearTable (src/table.cpp:52-110; test/test_table.cpp:104-121) on the device
  * for n abscissae (x, f: device pointers; the table itself is host data as in tpsrhs_chemistry).  Synchronous. */
 int tpsrhs_table_eval(const tpsrhs_table *table, int64_t n, const double *x, double *f);
+/* A two-dimensional table (tpsrhs_table2d) at n points (x[i], y[i]): what = 0 the value, 1 d/dx, 2 d/dy.  Host pointers;
+ * runs on the host, needs no device; the text the kernels of the two-dimensional table gas look their tables up with. */
+int tpsrhs_table2d_eval(const tpsrhs_table2d *table, int what, int64_t n, const double *x, const double *y, double *out);
 
 /* Diagnostic: the elementary functions the device closures are built on (tps_amd/csrc/fastmath.hpp; they replace
  * the libm calls of the reference's point physics -- pow / exp / log of src/collision_integrals.cpp:53-201,

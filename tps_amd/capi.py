@@ -140,6 +140,17 @@ class Lte(C.Structure):  # LteMixtureInput + the TableInputs of src/M2ulPhyS.cpp
                 ("viscosity_table", Table), ("conductivity_table", Table), ("electric_conductivity_table", Table)]
 
 
+class Table2D(C.Structure):  # tpsrhs_table2d: f[j * nx + i] at (x[i], y[j]), bilinear (GslTableInterpolator2D)
+    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("x", C.POINTER(C.c_double)), ("y", C.POINTER(C.c_double)),
+                ("f", C.POINTER(C.c_double))]
+
+
+class Lte2D(C.Structure):  # tpsrhs_lte2d: the (T, rho) tables of flow/lte/table_dim = 2; enabled = 1 selects them over `lte`
+    _fields_ = [("enabled", C.c_int), ("energy", Table2D), ("gas_constant", Table2D), ("sound_speed", Table2D),
+                ("temperature", Table2D), ("viscosity", Table2D), ("conductivity", Table2D),
+                ("electric_conductivity", Table2D)]
+
+
 class VisLayout(C.Structure):  # tpsrhs_vis_layout: first ROW of each group of tpsrhs_visualization_fields, -1 = absent
     _fields_ = [("nrows", C.c_int), ("Xsp", C.c_int), ("Ysp", C.c_int), ("nsp_", C.c_int), ("FluxTrns", C.c_int),
                 ("diffVel", C.c_int), ("SrcTrns", C.c_int), ("SpeciesTrns", C.c_int), ("rxn", C.c_int),
@@ -150,7 +161,7 @@ class Physics(C.Structure):
     _fields_ = [("eq_system", C.c_int), ("working_fluid", C.c_int), ("dry_air", DryAir), ("mixture", PerfectMixture),
                 ("transport_model", C.c_int), ("constant_transport", ConstantTransport),
                 ("gas_transport", GasTransport), ("chemistry", Chemistry), ("radiation", Radiation),
-                ("sgs", Sgs), ("visc_sponge", ViscSponge), ("lte", Lte)]
+                ("sgs", Sgs), ("visc_sponge", ViscSponge), ("lte", Lte), ("lte2d", Lte2D)]
 
 
 class BC(C.Structure):
@@ -282,6 +293,89 @@ def lte_physics(eq_system=NS, density="rho0p005", radiation=False) -> Physics:
     ph.lte.viscosity_table = make_table(tr[:, 0], tr[:, 1], keep=keep)
     ph.lte.conductivity_table = make_table(tr[:, 0], tr[:, 2], keep=keep)
     ph.lte.electric_conductivity_table = make_table(tr[:, 0], tr[:, 3], keep=keep)
+    if radiation:
+        nec = reference_table("nec_sample_0")
+        ph.radiation.model = NET_EMISSION
+        ph.radiation.nec_table = make_table(nec[:, 0], nec[:, 1], keep=keep)
+    ph._keep = keep
+    return ph
+
+
+_LTE2D_TABLES = None
+
+
+def lte2d_tables():
+    """The reference's own two-dimensional LTE tables (test/test_lte_mixture.cpp:16-30, test/inputs/plasma.lte2d.ini):
+    tests/golden/tables/lte_tables_2d.npz, written by make_lte_tables_2d.py next to it.  Axes and values f[j, i] at
+    (x[i], y[j]): thermo_{T,rho,e,R,c}, erev_{e,rho,T}, trans_{T,rho,mu,kappa,sigma}."""
+    global _LTE2D_TABLES
+    if _LTE2D_TABLES is None:
+        import os
+
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "tables", "lte_tables_2d.npz")
+        with np.load(path) as z:
+            _LTE2D_TABLES = {k: np.array(z[k]) for k in z.files}
+    return _LTE2D_TABLES
+
+
+def make_table2d(x, y, f, keep=None) -> Table2D:
+    """tpsrhs_table2d over float64 arrays x (nx), y (ny), f (ny, nx); `keep` (a list) receives the arrays so they outlive the call."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    assert x.ndim == 1 and y.ndim == 1 and f.shape == (len(y), len(x))
+    if keep is not None:
+        keep += [x, y, f]
+    return Table2D(len(x), len(y), x.ctypes.data_as(_dp), y.ctypes.data_as(_dp), f.ctypes.data_as(_dp))
+
+
+def table2d_eval(table, x, y, what=0) -> np.ndarray:
+    """tpsrhs_table2d_eval on the host: the value (what = 0), d/dx (1) or d/dy (2) of `table` at the points (x[i], y[i])"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    assert x.shape == y.shape and x.ndim == 1
+    out = np.empty_like(x)
+    lib = load()
+    st = lib.tpsrhs_table2d_eval(C.byref(table), int(what), x.size, x.ctypes.data_as(_dp), y.ctypes.data_as(_dp), out.ctypes.data_as(_dp))
+    if st != 0:
+        raise RuntimeError(lib.tpsrhs_last_error().decode())
+    return out
+
+
+def synthetic_transport_2d(T, rho, slices):
+    """SYNTHETIC transport with a density dependence (the reference's air_simple_transport_table.dat has none, and its sigma
+    column is zero): the mu and kappa slices times 1 + 0.3 rho, and for sigma an argon-like ramp, zero below 5000 K so that
+    the floor of 1 S/m is exercised, times the same factor.  Returns (mu, kappa, sigma), each (len(rho), len(T))."""
+    w = (1.0 + 0.3 * np.asarray(rho))[:, None]
+    sig = 0.35 * np.maximum(np.asarray(T) - 5000.0, 0.0) ** 1.1
+    return slices[0] * w, slices[1] * w, sig[None, :] * w
+
+
+def lte2d_physics(eq_system=NS, radiation=False, transport="reference") -> Physics:
+    """[flow] fluid = lte_table, lte/table_dim = 2 (the reference's default; test/inputs/plasma.lte2d.ini): argon
+    thermodynamics in (T, rho) of test/inputs/argon_lte_thermo_table.dat, the first guess T(e, rho) of
+    argon_lte_e_rev_table.dat, and the transport of air_simple_transport_table.dat ("reference": no density dependence,
+    sigma = 0) or the SYNTHETIC variant of synthetic_transport_2d ("synthetic")."""
+    t = lte2d_tables()
+    ph = Physics()
+    ph.eq_system = eq_system
+    ph.working_fluid = LTE_FLUID
+    ph.dry_air = DryAir(1.4, 287.058, 1.0, 0.0, 1.458e-6, 110.4, 0.71)  # unused by the table gas
+    keep = []
+    l2 = ph.lte2d
+    l2.enabled = 1
+    l2.energy = make_table2d(t["thermo_T"], t["thermo_rho"], t["thermo_e"], keep)
+    l2.gas_constant = make_table2d(t["thermo_T"], t["thermo_rho"], t["thermo_R"], keep)
+    l2.sound_speed = make_table2d(t["thermo_T"], t["thermo_rho"], t["thermo_c"], keep)
+    l2.temperature = make_table2d(t["erev_e"], t["erev_rho"], t["erev_T"], keep)
+    mu, kappa, sigma = t["trans_mu"], t["trans_kappa"], t["trans_sigma"]
+    if transport == "synthetic":
+        mu, kappa, sigma = synthetic_transport_2d(t["trans_T"], t["trans_rho"], (mu, kappa))
+    else:
+        assert transport == "reference", transport
+    l2.viscosity = make_table2d(t["trans_T"], t["trans_rho"], mu, keep)
+    l2.conductivity = make_table2d(t["trans_T"], t["trans_rho"], kappa, keep)
+    l2.electric_conductivity = make_table2d(t["trans_T"], t["trans_rho"], sigma, keep)
     if radiation:
         nec = reference_table("nec_sample_0")
         ph.radiation.model = NET_EMISSION
@@ -646,6 +740,7 @@ def load():
     lib.tpsrhs_mult_times.argtypes = [vp, C.c_int, _dp]
     lib.tpsrhs_eval_pointwise.argtypes = [vp, C.c_int, C.c_int64, vp, vp]
     lib.tpsrhs_table_eval.argtypes = [C.POINTER(Table), C.c_int64, vp, vp]
+    lib.tpsrhs_table2d_eval.argtypes = [C.POINTER(Table2D), C.c_int, C.c_int64, _dp, _dp, _dp]
     lib.tpsrhs_math_eval.argtypes = [C.c_int, C.c_int64, vp, vp]
     lib.tpsrhs_coulomb_eval.argtypes = [C.c_int, C.c_int64, vp, vp]
     lib.tpsrhs_kernel_bytes.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), _dp]
@@ -704,7 +799,7 @@ EXPORTED_SYMBOLS = [
     "tpsrhs_create", "tpsrhs_destroy", "tpsrhs_mult", "tpsrhs_mult_host", "tpsrhs_update_gradients",
     "tpsrhs_get_primitives", "tpsrhs_get_gradients", "tpsrhs_get_plasma_conductivity", "tpsrhs_height", "tpsrhs_num_dofs", "tpsrhs_num_equation",
     "tpsrhs_enable_kernel_timing", "tpsrhs_kernel_times", "tpsrhs_mult_times", "tpsrhs_kernel_bytes",
-    "tpsrhs_eval_pointwise", "tpsrhs_table_eval", "tpsrhs_math_eval", "tpsrhs_coulomb_eval", "tpsrhs_face_tables",
+    "tpsrhs_eval_pointwise", "tpsrhs_table_eval", "tpsrhs_table2d_eval", "tpsrhs_math_eval", "tpsrhs_coulomb_eval", "tpsrhs_face_tables",
     "tpsrhs_rk4_step", "tpsrhs_advance", "tpsrhs_step", "tpsrhs_advance_with", "tpsrhs_set_dt", "tpsrhs_set_forcing", "tpsrhs_set_joule_heating", "tpsrhs_set_mixing_length", "tpsrhs_status_string",
     "tpsrhs_last_error", "tpsrhs_version",
     "tpsrhs_stats_configure", "tpsrhs_stats_set_iter", "tpsrhs_stats_add_sample", "tpsrhs_stats_get", "tpsrhs_stats_set",

@@ -234,37 +234,49 @@ def dry_air_axisym(nr, nz, order, eq_system=capi.NS, wall_type=capi.VISC_ISOTH, 
 def lte_state(X, physics, seed=12345, amp=0.05, rho0=0.255, T0=7000.0, dT=4000.0, vel0=(1.0, 20.0, 3.0)):
     """Conserved state (5, NDofs) of the table gas in the axisymmetric formulation: smooth density, velocity (r, z, theta)
     and a temperature field T0 + dT * wave crossing many table intervals; rho e from the energy table (an INPUT state:
-    the kernels and the oracle each invert it themselves)."""
+    the kernels and the oracle each invert it themselves).  The density is rho0 (1 + amp * wave): amp = 0.6 for one that
+    varies strongly; an array `rho0` of one value per node is taken as it stands (exactly uniform, or two densities in one
+    state).  With two-dimensional tables (physics.lte2d.enabled) e = e(T, rho), bilinear."""
     wave = _waves(X, seed)
-    t = physics.lte.energy_table
-    Tt = np.ctypeslib.as_array(t.x_data, shape=(t.n_data,))
-    et = np.ctypeslib.as_array(t.f_data, shape=(t.n_data,))
-    rho = rho0 * (1.0 + amp * wave())
+    if np.ndim(rho0) > 0:
+        rho = np.array(rho0, dtype=np.float64)
+        wave()  # (the draws that follow do not depend on how the density was chosen)
+    else:
+        rho = rho0 * (1.0 + amp * wave())
     vref = max(abs(v) for v in vel0) or 1.0
-    vel = [v + amp * vref * wave() for v in vel0]
+    vel = [v + (amp if np.ndim(rho0) == 0 else 0.05) * vref * wave() for v in vel0]
     T = T0 + dT * wave()
+    if physics.lte2d.enabled:
+        e = capi.table2d_eval(physics.lte2d.energy, T, rho)
+    else:
+        t = physics.lte.energy_table
+        Tt = np.ctypeslib.as_array(t.x_data, shape=(t.n_data,))
+        et = np.ctypeslib.as_array(t.f_data, shape=(t.n_data,))
+        e = np.interp(T, Tt, et)
     U = np.zeros((5, X.shape[1]))
     U[0] = rho
     ke = 0.0
     for d in range(3):
         U[1 + d] = rho * vel[d]
         ke = ke + 0.5 * rho * vel[d] ** 2
-    U[4] = rho * np.interp(T, Tt, et) + ke
+    U[4] = rho * e + ke
     return U
 
 
 def lte_axisym(nr, nz, order, eq_system=capi.NS, wall_type=capi.VISC_ISOTH, r_in=0.0, r_out=0.05, length=0.25, warp=0.0,
-               radiation=False, density="rho0p255", name=None):
+               radiation=False, density="rho0p255", name=None, table_dim=1, transport="reference"):
     """Axisymmetric tube in the table gas (fluid = lte_table, the shape of the reference's test/inputs/plasma.lte1d.ini):
-    patch 1 inlet at z = 0 (density and velocity), 2 pressure outlet, 3 outer wall, 4 axis (inviscid wall)."""
+    patch 1 inlet at z = 0 (density and velocity), 2 pressure outlet, 3 outer wall, 4 axis (inviscid wall).
+    table_dim = 2: the two-dimensional (T, rho) tables (capi.lte2d_physics; `density` is not used)."""
     attrs = {(0, 0): 4, (0, 1): 3, (1, 0): 1, (1, 1): 2}
     mesh = meshgen.box_quad(nr, nz, lengths=(r_out - r_in, length), periodic=(False, False), bdr_attr=attrs, warp=warp,
                             origin=(r_in, 0.0))
     bcs = [capi.make_bc(1, capi.INLET, capi.SUB_DENS_VEL, [0.26, 0.0, 20.0, 2.0]),
            capi.make_bc(2, capi.OUTLET, capi.SUB_P, [3.6e5]), capi.make_bc(3, capi.WALL, wall_type, [3000.0]),
            capi.make_bc(4, capi.WALL, capi.INV)]
-    return Case(name or f"lte_axisym_{nr}x{nz}_p{order}", mesh, capi.Disc(order, 0, 0, 1, 0),
-                capi.lte_physics(eq_system, density, radiation), bcs, "axisymmetric table gas (LTE)")
+    ph = capi.lte2d_physics(eq_system, radiation, transport) if table_dim == 2 else capi.lte_physics(eq_system, density, radiation)
+    return Case(name or f"lte_axisym_{nr}x{nz}_p{order}", mesh, capi.Disc(order, 0, 0, 1, 0), ph, bcs,
+                "axisymmetric table gas (LTE)")
 
 
 def cylinder_bcs(wall_type=capi.VISC_ISOTH, t_wall=300.0, dim=3):

@@ -8,6 +8,7 @@
 #define TPSRHS_OPERATOR_PLAN_HPP_
 
 #include <cmath>
+#include <cstdint>
 #include <stdexcept>
 #include <string>
 
@@ -27,11 +28,52 @@ inline bool plan_is_non_reflecting(int category, int type) {
          (category == TPSRHS_OUTLET && (type == TPSRHS_SUB_P_NR || type == TPSRHS_SUB_MF_NR || type == TPSRHS_SUB_MF_NR_PW));
 }
 
+// a two-dimensional table as tpsrhs_table2d states it: both axes strictly increasing, at least one cell, finite data
+inline void check_table2d(const tpsrhs_table2d &t, const std::string &name) {
+  if (!t.x || !t.y || !t.f) throw std::invalid_argument(name + ": NULL pointer");
+  if (t.nx < 2 || t.ny < 2) throw std::invalid_argument(name + ": nx >= 2 and ny >= 2 (one cell at least)");
+  for (int i = 0; i < t.nx; i++)
+    if (!std::isfinite(t.x[i]) || (i > 0 && !(t.x[i] > t.x[i - 1]))) throw std::invalid_argument(name + ": x must be finite and strictly increasing");
+  for (int j = 0; j < t.ny; j++)
+    if (!std::isfinite(t.y[j]) || (j > 0 && !(t.y[j] > t.y[j - 1]))) throw std::invalid_argument(name + ": y must be finite and strictly increasing");
+  for (int64_t k = 0; k < static_cast<int64_t>(t.nx) * t.ny; k++)
+    if (!std::isfinite(t.f[k])) throw std::invalid_argument(name + ": non-finite value");
+}
+inline bool same_grid2d(const tpsrhs_table2d &a, const tpsrhs_table2d &b) {
+  if (a.nx != b.nx || a.ny != b.ny) return false;
+  for (int i = 0; i < a.nx; i++)
+    if (a.x[i] != b.x[i]) return false;
+  for (int j = 0; j < a.ny; j++)
+    if (a.y[j] != b.y[j]) return false;
+  return true;
+}
+// the tables of the two-dimensional table gas (tpsrhs_lte2d)
+inline void check_lte2d(const tpsrhs_lte2d &in) {
+  check_table2d(in.energy, "lte2d.energy");
+  check_table2d(in.gas_constant, "lte2d.gas_constant");
+  check_table2d(in.sound_speed, "lte2d.sound_speed");
+  check_table2d(in.temperature, "lte2d.temperature");
+  check_table2d(in.viscosity, "lte2d.viscosity");
+  check_table2d(in.conductivity, "lte2d.conductivity");
+  check_table2d(in.electric_conductivity, "lte2d.electric_conductivity");
+  for (int j = 0; j < in.energy.ny; j++)  // the Newton iteration of the temperature divides by de/dT
+    for (int i = 1; i < in.energy.nx; i++)
+      if (!(in.energy.f[j * in.energy.nx + i] > in.energy.f[j * in.energy.nx + i - 1]))
+        throw std::invalid_argument("lte2d.energy: e(T, rho) must increase with T on every density line");
+  // the reference reads e, R, c from the columns of one file and mu, kappa from those of another: one cell search serves
+  // the tables of a file
+  if (!same_grid2d(in.energy, in.gas_constant) || !same_grid2d(in.energy, in.sound_speed))
+    throw Unsupported("lte2d: energy, gas_constant and sound_speed must share their axes (the columns of one thermo file)");
+  if (!same_grid2d(in.viscosity, in.conductivity))
+    throw Unsupported("lte2d: viscosity and conductivity must share their axes (the columns of one transport file)");
+}
+
 struct OperatorPlan {
   int nc = 0;  // 1: the non-collocated Gauss-Lobatto pair, 0: the collocated Gauss-Legendre pair
   int dim = 0, order = 0, nvel = 0, neq = 0;
   int sp_first = 0, sp_last = 0;  // the species rows [sp_first, sp_last) of the state, which Check_Undershoot clamps; empty without a mixture
   bool plasma = false, lte = false;  // the working fluid; neither: dry air
+  bool lte2d = false;                // lte with the two-dimensional (T, rho) tables of tpsrhs_physics::lte2d
   bool heavy2d = false;              // 2-D kernels with the heavy closure interface: mixtures, axisymmetric dry air / table gas
   bool les = false;                  // dry air with a sub-grid scale model or a viscous sponge: the LES flavour of the kernels
   bool any_nr = false;               // some boundary condition is of a non-reflecting type
@@ -58,11 +100,14 @@ inline OperatorPlan plan_operator(int mesh_dim, const tpsrhs_disc &disc, const t
   else
     throw Unsupported("basisType / integrationRule: built pairs are (0, 0) Gauss-Legendre and (1, 1) Gauss-Lobatto");
   const bool axi = disc.axisymmetric != 0;
+  if (phys.working_fluid == TPSRHS_LTE_FLUID && phys.lte2d.enabled != 0 && (!axi || pl.nc))
+    throw Unsupported("WorkingFluid::LTE_FLUID (two-dimensional tables): built for the axisymmetric formulation, Gauss-Legendre pair");
   if (pl.nc && axi) throw Unsupported("the Gauss-Lobatto pair is built for the planar 2-D and the 3-D formulation");
   const bool plasma = pl.plasma = phys.working_fluid == TPSRHS_USER_DEFINED;
   if (axi && mesh_dim != 2) throw std::invalid_argument("the axisymmetric formulation needs a 2-D mesh");
   const bool lte = pl.lte = phys.working_fluid == TPSRHS_LTE_FLUID;
   if (phys.working_fluid != TPSRHS_DRY_AIR && !plasma && !lte) throw std::invalid_argument("unknown working_fluid");
+  const bool lte2d = pl.lte2d = lte && phys.lte2d.enabled != 0;  // (its scope: checked above, ahead of the general refusals)
   if (lte && (!axi || pl.nc))
     throw Unsupported("WorkingFluid::LTE_FLUID (one-dimensional tables): built for the axisymmetric formulation, Gauss-Legendre pair");
   if (disc.use_roe && (mesh_dim != 2 || axi || plasma || lte))
@@ -160,7 +205,9 @@ inline OperatorPlan plan_operator(int mesh_dim, const tpsrhs_disc &disc, const t
   if (heavy && v.enabled && (!pl.heavy2d || pl.nc))
     throw Unsupported("viscous sponge for mixtures: built for the planar 2-D and the axisymmetric formulation, Gauss-Legendre pair");
   if (pl.heavy2d && v.enabled) sponge_plane();
-  if (lte) {
+  if (lte2d) {
+    check_lte2d(phys.lte2d);
+  } else if (lte) {
     const tpsrhs_lte &in = phys.lte;
     // LinearTable with xLogScale = fLogScale = false, as the reference hard-codes for these tables (src/M2ulPhyS.cpp:176-255);
     // the inverse table T(e) and its search aid assume linear axes

@@ -14,6 +14,7 @@
 
 #include "physics_dryair.hpp"
 #include "physics_plasma.hpp"  // TableDev, table_eval (LinearTable on the device)
+#include "table2d.hpp"         // the two-dimensional tables and the closures that look them up
 
 namespace tpsrhs {
 
@@ -119,9 +120,21 @@ __device__ inline double lte_temperature_rho_p(const LP &p, double rho, double p
   return T;
 }
 
-// LTE_ = false: dry air (gamma law, Sutherland); true: the table gas
-template <bool LTE_>
+// ---- WorkingFluid::LTE_FLUID with two-dimensional tables in (T, rho) (flow/lte/table_dim = 2, the reference's default, which
+// its own device build refuses, src/M2ulPhyS.cpp:166-170): the same gas with bilinear tables (table2d.hpp).  Every look-up
+// takes the density of the state it is given -- the call sites are listed in DESIGN.md section 1.  The tables stay in global
+// memory, their records travel in the parameter image; the net-emission table stays one-dimensional in T.
+struct Lte2dParams : DryAirParams, Lte2dTables {
+  TableDev tab_nec;
+  int radiation;
+};
+
+// GAS = false: dry air (gamma law, Sutherland); true: the table gas, one-dimensional tables; 2: two-dimensional tables.
+// (`auto`: GasAxiPhys<false> and GasAxiPhys<true> are the types, and their kernels and functions the symbols, they were
+// when the parameter was a bool and there was no third flavour -- the device code of the two is compared by symbol.)
+template <auto GAS>
 struct GasAxiPhys {
+  static constexpr bool LTE_ = static_cast<int>(GAS) != 0, T2D_ = static_cast<int>(GAS) == 2;
   static constexpr int DIM = 2, NVEL = 3, NEQ = 5, NACTIVE = 0, ITH = 4;
   static constexpr bool HAS_SOURCE = true, AXISYM = true, HEAVY = true, TWO_TEMPERATURE = false, HAS_NR_BC = false;
   static constexpr bool TWO_STEP = false;
@@ -135,7 +148,7 @@ struct GasAxiPhys {
   static constexpr bool LES = false;  // sub-grid scale models / viscous sponge: dry air, planar and 3-D
   static constexpr bool HAS_MIXED_OUT = false;  // mixed-out sponge target: dry air, planar / 3-D
   static constexpr bool LTE = LTE_;
-  typedef std::conditional_t<LTE_, LteParams, DryAirParams> Params;
+  typedef std::conditional_t<T2D_, Lte2dParams, std::conditional_t<LTE_, LteParams, DryAirParams>> Params;
   // The table gas reads its parameter block -- eight table records, 70-180 spilled SGPRs when it travelled by value in the
   // kernel-argument segment (round 3) -- from a device image through the CONSTANT address space, like the plasma kernels
   // (PlasmaPhys::KArg); dry air keeps the by-value block.
@@ -159,12 +172,18 @@ struct GasAxiPhys {
       return p;
     }
   }
-  struct State {
+  struct NoCell {};
+  struct Cell2d {
+    double rho, dx, dy;  // two-dimensional tables: the density of the state and its offsets in its cell of the thermodynamic grid
+  };
+  struct State : std::conditional_t<T2D_, Cell2d, NoCell> {
     double ir, k, p;
     double vel[NVEL];
     double T;  // table gas only
-    int it;    // ... and the interval of T in the grid of the thermodynamic tables
+    int it;    // ... and the interval of T in the grid of the thermodynamic tables (two-dimensional: the record of the cell)
   };
+  // a thermodynamic table at the (T, rho) of a state
+  __device__ static inline double thermo2d(const BilinearCell *cells, const State &s) { return cell_value(cells[s.it], s.dx, s.dy); }
   __device__ static inline State make_state(PRef p, const double *U) {
     State s;
     s.ir = fast_rcp(U[0]);
@@ -175,7 +194,15 @@ struct GasAxiPhys {
       s.vel[d] = U[1 + d] * s.ir;
     }
     s.k = m2 * s.ir;
-    if constexpr (LTE_) {  // LteMixture::ComputePressure, src/lte_mixture.cpp:119-131
+    if constexpr (T2D_) {  // LteMixture::ComputePressure, src/lte_mixture.cpp:119-135, at the density of this state
+      ThermoCell tc;
+      s.rho = U[0];
+      s.T = lte2d_temperature(p, (U[ITH] - 0.5 * s.k) / U[0], U[0], cell_y(p.g_th, U[0]), tc);
+      s.it = tc.k;
+      s.dx = tc.dx;
+      s.dy = tc.dy;
+      s.p = U[0] * thermo2d(p.c_R, s) * s.T;
+    } else if constexpr (LTE_) {  // LteMixture::ComputePressure, src/lte_mixture.cpp:119-131
       s.T = lte_temperature(p, (U[ITH] - 0.5 * s.k) / U[0], s.it);
       s.p = U[0] * lte_thermo_at(p, p.tab_R, s.it, s.T) * s.T;
     } else {
@@ -192,7 +219,12 @@ struct GasAxiPhys {
       return s.p * p.inv_Rg * s.ir;
   }
   __device__ static inline double rho_e_at_pressure(PRef p, double rho, double pres) {
-    if constexpr (LTE_)
+    if constexpr (T2D_) {  // src/lte_mixture.cpp:453-470: T and e at the density handed in
+      ThermoCell tc;
+      const double T = lte2d_temperature_rho_p(p, rho, pres, tc);
+      (void)T;
+      return rho * cell_value(p.c_e[tc.k], tc.dx, tc.dy);
+    } else if constexpr (LTE_)
     {
       int it;  // (the interval is R's: e shares it when the tables share their grid)
       const double T = lte_temperature_rho_p(p, rho, pres, it);
@@ -202,13 +234,17 @@ struct GasAxiPhys {
       return pres / (p.gamma - 1.0);
   }
   __device__ static inline double rho_e_at_temperature(PRef p, double rho, double T) {
-    if constexpr (LTE_)
+    if constexpr (T2D_)
+      return rho * table2d_at(p.g_th, p.c_e, T, rho);  // src/lte_mixture.cpp:430-446
+    else if constexpr (LTE_)
       return rho * table_eval(p.tab_e, T);  // src/lte_mixture.cpp:424-441
     else
       return p.Rg / (p.gamma - 1.0) * rho * T;
   }
   __device__ static inline double sound(PRef p, const State &s) {
-    if constexpr (LTE_)
+    if constexpr (T2D_)
+      return thermo2d(p.c_c, s);  // src/lte_mixture.cpp:366-381
+    else if constexpr (LTE_)
       return lte_thermo_at(p, p.tab_c, s.it, s.T);  // src/lte_mixture.cpp:357-372
     else
       return fast_sqrt(p.gamma * s.p * s.ir);
@@ -272,7 +308,13 @@ struct GasAxiPhys {
   }
   // Sutherland viscosity, bulk viscosity and conductivity at the temperature of a conserved state
   __device__ static inline void transport(PRef p, const State &s, double &visc, double &bulk, double &k) {
-    if constexpr (LTE_) {  // LteTransport::ComputeFluxMolecularTransport, src/lte_transport_properties.cpp:84-107
+    if constexpr (T2D_) {  // LteTransport::ComputeFluxMolecularTransport, src/lte_transport_properties.cpp:84-105
+      const AxisCell cx = cell_x(p.g_tr, s.T), cy = cell_y(p.g_tr, s.rho);
+      const int km = cy.i * (p.g_tr.nx - 1) + cx.i;
+      visc = cell_value(p.c_mu[km], cx.d, cy.d);
+      bulk = 0.0;
+      k = cell_value(p.c_k[km], cx.d, cy.d);
+    } else if constexpr (LTE_) {  // LteTransport::ComputeFluxMolecularTransport, src/lte_transport_properties.cpp:84-107
       const int im = table_interval(p.tab_mu, s.T);
       visc = table_at(p.tab_mu, im, s.T);
       bulk = 0.0;
@@ -446,7 +488,10 @@ struct GasAxiPhys {
   }
   // SrcTrns::ELECTRIC_CONDUCTIVITY: LteTransport::ComputeSourceMolecularTransport, src/lte_transport_properties.cpp:109-126
   __device__ static inline double electric_conductivity(PRef p, const double *U) {
-    if constexpr (LTE_) {
+    if constexpr (T2D_) {
+      const double sigma = table2d_at(p.g_sig, p.c_sigma, make_state(p, U).T, U[0]);
+      return sigma < 1.0 ? 1.0 : sigma;
+    } else if constexpr (LTE_) {
       const double sigma = table_eval(p.tab_sigma, make_state(p, U).T);
       return sigma < 1.0 ? 1.0 : sigma;
     } else {
@@ -457,14 +502,19 @@ struct GasAxiPhys {
                                               double radius, double *src) {
     const double rho = Up[0], ur = Up[1], ut = Up[3];
     double pres;
-    if constexpr (LTE_)
+    if constexpr (T2D_)
+      pres = Up[0] * table2d_at(p.g_th, p.c_R, Up[ITH], Up[0]) * Up[ITH];  // src/lte_mixture.cpp:142-151
+    else if constexpr (LTE_)
       pres = Up[0] * table_eval(p.tab_R, Up[ITH]) * Up[ITH];  // LteMixture::ComputePressureFromPrimitives, src/lte_mixture.cpp:138-147
     else
       pres = p.Rg * Up[0] * Up[ITH];  // DryAir::ComputePressureFromPrimitives
     double tau_tt = 0.0, tau_tr = 0.0;
     if (p.eq_system != TPSRHS_EULER) {
       double visc, bulkv, k;
-      if constexpr (LTE_) {  // LteTransport::GetViscosities, src/lte_transport_properties.cpp:128-140: at the primitive T
+      if constexpr (T2D_) {  // LteTransport::GetViscosities, src/lte_transport_properties.cpp:125-136: at the primitive T, rho
+        visc = table2d_at(p.g_tr, p.c_mu, Up[ITH], Up[0]);
+        bulkv = 0.0;
+      } else if constexpr (LTE_) {  // LteTransport::GetViscosities, src/lte_transport_properties.cpp:128-140: at the primitive T
         visc = table_eval(p.tab_mu, Up[ITH]);
         bulkv = 0.0;
       } else {
@@ -485,6 +535,7 @@ struct GasAxiPhys {
 };
 typedef GasAxiPhys<false> DryAirAxiPhys;
 typedef GasAxiPhys<true> LteAxiPhys;
+typedef GasAxiPhys<2> Lte2dAxiPhys;
 
 }  // namespace tpsrhs
 #endif

@@ -2,7 +2,9 @@
 // routes of the Coulomb fits, coulomb_table.hpp) and tpsrhs_table_eval (LinearTable on the device).  They take no operator
 // and run on the NULL stream of the current device.
 #include "abi_support.hpp"
+#include "operator_plan.hpp"  // check_table2d
 #include "physics_plasma.hpp"
+#include "table2d.hpp"
 
 #include <algorithm>
 
@@ -117,6 +119,18 @@ int tpsrhs_table_eval(const tpsrhs_table *table, int64_t n, const double *x, dou
       HIP_CHECK(hipGetLastError());
     }
     HIP_CHECK(hipDeviceSynchronize());
+  });
+}
+
+// GslTableInterpolator2D::eval / eval_x / eval_y with the bilinear interpolant (src/table.cpp:262-300), on the host: the text
+// of table2d.hpp the kernels of the two-dimensional table gas run
+int tpsrhs_table2d_eval(const tpsrhs_table2d *table, int what, int64_t n, const double *x, const double *y, double *out) {
+  if (!table || n < 0 || !x || !y || !out || what < 0 || what > 2) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "table2d_eval");
+  return guarded([&] {
+    check_table2d(*table, "tpsrhs_table2d_eval");
+    const Grid2Dev g = make_grid2d(*table, [](const void *src, size_t) { return src; });  // (the caller's axes, in place)
+    const std::vector<BilinearCell> cells = make_cells(*table);
+    for (int64_t i = 0; i < n; i++) out[i] = table2d_at(g, cells.data(), x[i], y[i], what);
   });
 }
 

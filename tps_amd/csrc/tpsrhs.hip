@@ -31,6 +31,7 @@
 // loaded when an operator of that family is created: load_family below.
 void pick_dryair_axisym(tpsrhs_operator *op);
 void pick_lte_axisym(tpsrhs_operator *op);
+void pick_lte2d_axisym(tpsrhs_operator *op);
 void pick_dryair_les(tpsrhs_operator *op);
 
 TableDev upload_table(std::vector<DevBuf<void>> &owner, const tpsrhs_table &t) {
@@ -206,6 +207,17 @@ void upload_lte_tables(tpsrhs_operator *op, LteParams *lp, const tpsrhs_physics 
   if (lp->radiation == TPSRHS_NET_EMISSION) lp->tab_nec = upload_table(op->d_extra, phys->radiation.nec_table);
 }
 
+// the two-dimensional tables of the table gas (the plan has validated them): the axes and the cell records to the device
+void upload_lte2d_tables(tpsrhs_operator *op, Lte2dParams *lp, const tpsrhs_physics *phys) {
+  static_cast<Lte2dTables &>(*lp) = make_lte2d_tables(phys->lte2d, [op](const void *src, size_t bytes) {
+    const unsigned char *b = static_cast<const unsigned char *>(src);
+    op->d_extra.emplace_back(DevBuf<unsigned char>(std::vector<unsigned char>(b, b + bytes)));
+    return static_cast<const void *>(op->d_extra.back().get());
+  });
+  lp->radiation = phys->radiation.model;
+  if (lp->radiation == TPSRHS_NET_EMISSION) lp->tab_nec = upload_table(op->d_extra, phys->radiation.nec_table);
+}
+
 // Fluxes: sub-grid scale model and viscous sponge (src/fluxes.cpp:223-246) -> the LES flavour of the dry-air kernels
 void fill_les_params(tpsrhs_operator *op, const OperatorPlan &pl, DryAirParams &d, const tpsrhs_mesh *mesh, const tpsrhs_physics *phys) {
   d.sgs_type = phys->sgs.model_type;
@@ -229,12 +241,15 @@ void fill_les_params(tpsrhs_operator *op, const OperatorPlan &pl, DryAirParams &
 // the dry-air block, which the table gas extends (boundary conditions and switches are shared)
 void fill_single_fluid_params(tpsrhs_operator *op, const OperatorPlan &pl, const tpsrhs_mesh *mesh, const tpsrhs_disc *disc,
                               const tpsrhs_physics *phys, int num_bcs, const tpsrhs_bc *bcs) {
-  static_assert(sizeof(LteParams) <= sizeof(op->params), "parameter block");
-  LteParams *lp = pl.lte ? new (op->params) LteParams : nullptr;
+  static_assert(sizeof(LteParams) <= sizeof(op->params) && sizeof(Lte2dParams) <= sizeof(op->params), "parameter block");
+  LteParams *lp = (pl.lte && !pl.lte2d) ? new (op->params) LteParams : nullptr;
   if (lp) std::memset(static_cast<void *>(lp), 0, sizeof(LteParams));
-  DryAirParams &d = lp ? *static_cast<DryAirParams *>(lp) : *new (op->params) DryAirParams;
-  if (!lp) std::memset(&d, 0, sizeof(d));
+  Lte2dParams *lp2 = pl.lte2d ? new (op->params) Lte2dParams : nullptr;
+  if (lp2) std::memset(static_cast<void *>(lp2), 0, sizeof(Lte2dParams));
+  DryAirParams &d = lp ? *static_cast<DryAirParams *>(lp) : (lp2 ? *static_cast<DryAirParams *>(lp2) : *new (op->params) DryAirParams);
+  if (!lp && !lp2) std::memset(&d, 0, sizeof(d));
   if (lp) upload_lte_tables(op, lp, phys);
+  if (lp2) upload_lte2d_tables(op, lp2, phys);
   d.gamma = phys->dry_air.specific_heat_ratio;
   d.Rg = phys->dry_air.gas_constant;
   d.inv_Rg = 1.0 / d.Rg;
@@ -403,6 +418,8 @@ void setup(tpsrhs_operator *op, const tpsrhs_mesh *mesh, const tpsrhs_disc *disc
     fill_single_fluid_params(op, pl, mesh, disc, phys, num_bcs, bcs);
     if (pl.les)
       pick_dryair_les(op);
+    else if (pl.lte2d)
+      pick_lte2d_axisym(op);
     else if (pl.lte)
       pick_lte_axisym(op);
     else if (disc->axisymmetric)
