@@ -911,6 +911,52 @@ int tpsrhs_set_reaction_rates(tpsrhs_handle h, const double *rates, int num_comp
  * Asynchronous on the operator's stream.  Dry air and the table gas: TPSRHS_ERR_UNSUPPORTED. */
 int tpsrhs_boltzmann_fields(tpsrhs_handle h, const double *x, int num_species, double *out);
 
+/* ---- restart of a species plasma from an LTE solution (`io/restartFromLTE = True`) --------------------------------------
+ * The reference reads only rho, rho u, rho E of such a restart file (the species rows and rhoE_e are optional,
+ * src/M2ulPhyS.cpp:1842-1853), and M2ulPhyS::initilizeSpeciesFromLTE (:2388-2461) rebuilds every node with
+ * PerfectMixture::GetSpeciesFromLTE -- a serial host loop that needs GSL and is compiled out of its CUDA and HIP builds.
+ * Here both forms of that routine run on the device, for USER_DEFINED mixtures in the routine's species order: the ion of
+ * charge +1 at num_species - 3, the electron at num_species - 2, the neutral background last, every species before the ion
+ * an excited level of the neutral (src/equation_of_state.cpp:1952-1970).  Dry air, the table gas, and a mixture in another
+ * order (a charged species below num_species - 3, no +1 ion at num_species - 3, no electron): TPSRHS_ERR_UNSUPPORTED, the
+ * message names the species.  NULL handle or array, n < 0: TPSRHS_ERR_INVALID_ARGUMENT.  All refusals come before any
+ * device work.  Both entry points are ordered on the operator's stream and synchronous on return.
+ *
+ * The tables: the thermo file's columns 3 (e) and 6 (R) over (T, rho) and the e_rev file's T over (e, rho)
+ * (flow/lte/thermo_table, flow/lte/e_rev_table; src/M2ulPhyS.cpp:2414-2429).  Host pointers, copied for the duration of the
+ * call.  The sound-speed table the reference also passes in is never read (src/equation_of_state.cpp:1944-2094) and is not
+ * asked for.  Each table must satisfy tpsrhs_table2d and the energy must increase with T on every density line:
+ * TPSRHS_ERR_INVALID_ARGUMENT otherwise; `energy` and `gas_constant` on different axes: TPSRHS_ERR_UNSUPPORTED (as
+ * tpsrhs_lte2d). */
+typedef struct tpsrhs_lte_restart {   /* flow/lte/thermo_table columns 3 and 6, flow/lte/e_rev_table */
+  tpsrhs_table2d energy, gas_constant, temperature;
+} tpsrhs_lte_restart;
+/* num_not_converged: nodes whose Newton iteration for T did not converge in 20 steps (the reference prints a warning and goes
+ * on with the last iterate, :2024-2027; so does this library).  num_invalid: nodes where the reference would have hit one of
+ * its asserts -- T <= 0 in the Newton loop (:2014), n_e < 0, some n_sp < 0, |n_0 - sum n_sp| / n_0 >= 1e-14 (:2181-2186);
+ * their rows hold what the arithmetic gave.  max_density_change = max |rho_new / rho - 1|: the tables and the mixture may
+ * carry different excited levels, so T and p are kept and the density moves "a few tenths of a percent"; larger values point
+ * to a mistake in the input (:2048-2057).  t_min, t_max: the extrema of the temperature found.  Reduced on the device in a
+ * fixed order: the same state gives the same report. */
+typedef struct tpsrhs_lte_restart_report {
+  int64_t num_not_converged, num_invalid;
+  double max_density_change, t_min, t_max;
+} tpsrhs_lte_restart_report;
+/* PerfectMixture::GetSpeciesFromLTE(T, p, n_sp), src/equation_of_state.cpp:2096-2187 (also the start of the reference's
+ * low-Mach reacting solver, src/reactingFlow.cpp:1909-1921): the electron density from the Saha equation, the levels of the
+ * neutral from the Boltzmann distribution with TPSRHS_SPECIES_DEGENERACY and TPSRHS_FORMATION_ENERGY, in the reference's
+ * order of operations.  T [K], p [Pa]: DEVICE [n].  n_sp_out: DEVICE [num_species][n], mol/m^3. */
+int tpsrhs_lte_composition(tpsrhs_handle h, int64_t n, const double *T, const double *p, double *n_sp_out);
+/* PerfectMixture::GetSpeciesFromLTE(conserv, primit, tables) at every node (src/equation_of_state.cpp:1944-2094,
+ * src/M2ulPhyS.cpp:2441-2455), then the species clamp of Check_Undershoot (:2526-2548) on the new state.  x: DEVICE
+ * [num_equation][NDofs], the layout of tpsrhs_mult, updated in place: on entry only the rows 0 .. nvel + 1 (rho, rho u,
+ * rho E of the LTE solution) are read, every row is written -- T from the tables by Newton, p = rho R(T, rho) T, the
+ * composition at (T, p), then rho, rho u (velocity unchanged), rho E, rho Y_sp and, two temperatures, rhoE_e = n_e c_v,e T.
+ * up_out: DEVICE [num_equation][NDofs] or NULL, the primitives of the new state (rho, u, T, n_sp, T_e = T).  report: HOST,
+ * or NULL. */
+int tpsrhs_species_from_lte(tpsrhs_handle h, const tpsrhs_lte_restart *tables, double *x, double *up_out,
+                            tpsrhs_lte_restart_report *report);
+
 /* Host-only view of the face topology tpsrhs_create derives from a mesh (the role of the
  * indirection arrays of src/M2ulPhyS.cpp:816-1486); touches no device.  Outputs (caller-allocated):
  *   face_nbr[ne*2*dim]   >= 0: trace slot (element*2*dim + local face) of the neighbour, slots

@@ -186,6 +186,16 @@ class RHSoperatorHIP : public mfem::TimeDependentOperator {
     check(tpsrhs_set_reaction_rates(h_, rates ? rates->Read() : nullptr, rates ? num_components : 0,
                                     (rates && num_components > 0) ? static_cast<int64_t>(rates->Size()) / num_components : ndofs));
   }
+  // M2ulPhyS::initilizeSpeciesFromLTE (src/M2ulPhyS.cpp:2388-2461; io/restartFromLTE) followed by Check_Undershoot: U holds
+  // rho, rho u, rho E of the LTE solution in its first nvel + 2 variables and is rebuilt in place; Up (optional) takes the
+  // primitives.  `tables`: flow/lte/thermo_table columns 3 and 6, flow/lte/e_rev_table, host arrays.  The report is returned;
+  // the reference only prints a warning for a node that does not converge, so nothing is thrown for one.
+  tpsrhs_lte_restart_report initializeSpeciesFromLTE(const tpsrhs_lte_restart &tables, mfem::Vector &U, mfem::Vector *Up = nullptr) {
+    tpsrhs_lte_restart_report report = {};
+    (void)U.Read();  // the device copy is current; Write() then hands out the same array and marks it as the valid one
+    check(tpsrhs_species_from_lte(h_, &tables, U.Write(), Up ? Up->Write() : nullptr, &report));
+    return report;
+  }
   tpsrhs_handle handle() const { return h_; }
   int num_equation() const { return tpsrhs_num_equation(h_); }
 

@@ -151,6 +151,15 @@ class Lte2D(C.Structure):  # tpsrhs_lte2d: the (T, rho) tables of flow/lte/table
                 ("electric_conductivity", Table2D)]
 
 
+class LteRestart(C.Structure):  # tpsrhs_lte_restart: thermo file columns 3 (e) and 6 (R) over (T, rho), e_rev file T over (e, rho)
+    _fields_ = [("energy", Table2D), ("gas_constant", Table2D), ("temperature", Table2D)]
+
+
+class LteRestartReport(C.Structure):  # tpsrhs_lte_restart_report
+    _fields_ = [("num_not_converged", C.c_int64), ("num_invalid", C.c_int64), ("max_density_change", C.c_double),
+                ("t_min", C.c_double), ("t_max", C.c_double)]
+
+
 class VisLayout(C.Structure):  # tpsrhs_vis_layout: first ROW of each group of tpsrhs_visualization_fields, -1 = absent
     _fields_ = [("nrows", C.c_int), ("Xsp", C.c_int), ("Ysp", C.c_int), ("nsp_", C.c_int), ("FluxTrns", C.c_int),
                 ("diffVel", C.c_int), ("SrcTrns", C.c_int), ("SpeciesTrns", C.c_int), ("rxn", C.c_int),
@@ -523,7 +532,7 @@ def argon_ternary_physics(eq_system=NS, two_temperature=False, transport=ARGON_M
 
 
 def argon_levels_physics(levels=3, ambipolar=False, eq_system=NS, transport=CONSTANT, two_temperature=True, reactions=True,
-                         radiation=False, third_order_ke=True) -> Physics:
+                         radiation=False, third_order_ke=True, ion_last=False) -> Physics:
     """Argon with `levels` (0..5) excited neutral levels: mixture order Ar.+1, [Ar_m, Ar_r, Ar_p, Ar_h1, Ar_h2][:levels], E, Ar.
     levels = 4, 5 (seven / eight species, the MAXSPECIES = 8 of the reference's device build): two further lumped
     neutral levels between Ar_p and the ion -- SYNTHETIC, the reference ships no compressible-solver input with more
@@ -532,20 +541,24 @@ def argon_levels_physics(levels=3, ambipolar=False, eq_system=NS, transport=CONS
     levels = 2, not ambipolar: the five species of test/inputs/input.malamas.test.ini; the ambipolar variants drop
     the electron equation (four species: the count of test/inputs/perfectGas.argon.ini).  Transport: constant
     coefficients or the argon collision table (every neutral-neutral pair AR_AR, neutral-ion AR_AR1P,
-    neutral-electron AR_E)."""
+    neutral-electron AR_E).  ion_last: the ion after the levels, the order of argon_lte_restart_physics."""
     ph = Physics()
     ph.eq_system = eq_system
     ph.working_fluid = USER_DEFINED
     m_ar, m_e = 39.948e-3, 5.48579908782496e-7
     nsp = 3 + levels
     ie, ib = nsp - 2, nsp - 1
+    lvn = ["m", "r", "p", "h1", "h2"][:levels]
+    names = (lvn + ["ion"] if ion_last else ["ion"] + lvn) + ["e", "ar"]
+    ii = names.index("ion")
     mx = ph.mixture
     mx.num_species, mx.is_electron_included, mx.ambipolar, mx.two_temperature = nsp, 1, int(ambipolar), int(two_temperature)
-    lv = list(range(1, 1 + levels))  # mixture indices of the excited levels
-    mw = [m_ar - m_e] + [m_ar] * levels + [m_e, m_ar]
-    charge = [1.0] + [0.0] * levels + [-1.0, 0.0]
-    eform = [1520571.3883] + [1116860.96186, 1130867.391486, 1269949.8858896866, 1361000.0, 1420000.0][:levels] + [0.0, 0.0]
-    degen = [4.0] + [6.0, 6.0, 36.0, 60.0, 100.0][:levels] + [1.0, 1.0]
+    # per species name: mass, charge, formation energy [J/mol], degeneracy, (constant diffusivity, momentum-transfer frequency)
+    data = {"ion": (m_ar - m_e, 1.0, 1520571.3883, 4.0, (3.0e-3, 1.0e9)), "m": (m_ar, 0.0, 1116860.96186, 6.0, (2.6e-3, 3.0e8)),
+            "r": (m_ar, 0.0, 1130867.391486, 6.0, (2.7e-3, 3.5e8)), "p": (m_ar, 0.0, 1269949.8858896866, 36.0, (2.8e-3, 3.2e8)),
+            "h1": (m_ar, 0.0, 1361000.0, 60.0, (2.9e-3, 3.1e8)), "h2": (m_ar, 0.0, 1420000.0, 100.0, (3.1e-3, 2.9e8)),
+            "e": (m_e, -1.0, 0.0, 1.0, (2.0e-1, 0.0)), "ar": (m_ar, 0.0, 0.0, 1.0, (2.5e-3, 4.0e8))}
+    mw, charge, eform, degen, df = ([data[k][c] for k in names] for c in range(5))
     for sp in range(nsp):
         mx.gas_params[sp + SPECIES_MW * nsp] = mw[sp]
         mx.gas_params[sp + SPECIES_CHARGES * nsp] = charge[sp]
@@ -556,14 +569,12 @@ def argon_levels_physics(levels=3, ambipolar=False, eq_system=NS, transport=CONS
     ct = ph.constant_transport
     ct.viscosity, ct.bulk_viscosity = 5.0e-5, 1.0e-5
     ct.thermal_conductivity, ct.electron_thermal_conductivity = 0.05, 0.2
-    df = [(3.0e-3, 1.0e9)] + [(2.6e-3, 3.0e8), (2.7e-3, 3.5e8), (2.8e-3, 3.2e8), (2.9e-3, 3.1e8), (3.1e-3, 2.9e8)][:levels] + \
-         [(2.0e-1, 0.0), (2.5e-3, 4.0e8)]
     for sp, (d, f) in enumerate(df):
         ct.diffusivity[sp], ct.mt_freq[sp] = d, f
     ct.electron_index = ie
     gt = ph.gas_transport
-    gt.neutral_index, gt.ion_index, gt.electron_index = ib, 0, ie
-    kinds = ["ion"] + ["n"] * levels + ["e", "n"]
+    gt.neutral_index, gt.ion_index, gt.electron_index = ib, ii, ie
+    kinds = [k if k in ("ion", "e") else "n" for k in names]
     rule = {("ion", "ion"): CLMB_REP, ("ion", "n"): AR_AR1P, ("ion", "e"): CLMB_ATT, ("n", "n"): AR_AR, ("n", "e"): AR_E,
             ("e", "e"): CLMB_REP, ("n", "ion"): AR_AR1P, ("e", "ion"): CLMB_ATT, ("e", "n"): AR_E}
     for i in range(nsp):
@@ -578,7 +589,6 @@ def argon_levels_physics(levels=3, ambipolar=False, eq_system=NS, transport=CONS
     ch.electron_index = ie
     ch.minimum_temperature = 2000.0
     keep = []
-    names = ["ion"] + ["m", "r", "p", "h1", "h2"][:levels] + ["e", "ar"]
     if reactions == "tabulated":  # the tabulated reactions of test/inputs/input.radDecay.ini among the present species
         rxn = [r for r in RADDECAY_REACTIONS if all(k in names for k in list(r[0]) + list(r[1]))]
         ch.num_reactions = len(rxn)
@@ -619,6 +629,43 @@ def argon_levels_physics(levels=3, ambipolar=False, eq_system=NS, transport=CONS
         ph.radiation.nec_table = reference_nec_table(keep)
     ph._keep = keep
     return ph
+
+
+LTE_RESTART_SPECIES = ("Ar_m", "Ar_r", "Ar_p", "Ar.+1", "E", "Ar")
+
+
+def argon_lte_restart_physics(levels=3, ambipolar=True, two_temperature=False, eq_system=NS, transport=CONSTANT, reactions=True,
+                              radiation=False) -> Physics:
+    """The mixture of test/inputs/argon.plasma.lte2noneq.ini:126-231 (`io/restartFromLTE = True`) in the order the reference
+    gives it (src/M2ulPhyS.cpp:3114-3236): [Ar_m, Ar_r, Ar_p][:levels], Ar.+1, E, Ar -- the ion at numSpecies - 3, where
+    PerfectMixture::GetSpeciesFromLTE looks for it.  Degeneracies 6, 6, 36, 4, 1, 1; masses and formation energies of that
+    input (those of argon_levels_physics, which puts the ion first).  The input is ambipolar with one temperature."""
+    assert 0 <= levels <= 3
+    return argon_levels_physics(levels, ambipolar, eq_system, transport, two_temperature, reactions, radiation, ion_last=True)
+
+
+def lte_restart_species_names(physics):
+    """the names of the active species of an argon_lte_restart_physics mixture, in row order (`rho-Y_<name>` in a restart file)"""
+    mx = physics.mixture
+    names = LTE_RESTART_SPECIES[:mx.num_species - 3] + LTE_RESTART_SPECIES[3:]
+    return list(names[:mx.num_species - 2 if mx.ambipolar else mx.num_species - 1])
+
+
+def make_lte_restart(energy, gas_constant, temperature, keep=None) -> LteRestart:
+    """tpsrhs_lte_restart from three (x, y, f) triples of float64 arrays, f of shape (len(y), len(x))"""
+    t = LteRestart()
+    keep = t._keep = [] if keep is None else keep
+    t.energy = make_table2d(*energy, keep=keep)
+    t.gas_constant = make_table2d(*gas_constant, keep=keep)
+    t.temperature = make_table2d(*temperature, keep=keep)
+    return t
+
+
+def lte_restart_tables(keep=None) -> LteRestart:
+    """the tables of lte2d_tables() that a restart from LTE reads: e(T, rho), R(T, rho), T(e, rho)"""
+    t = lte2d_tables()
+    return make_lte_restart((t["thermo_T"], t["thermo_rho"], t["thermo_e"]), (t["thermo_T"], t["thermo_rho"], t["thermo_R"]),
+                            (t["erev_e"], t["erev_rho"], t["erev_T"]), keep)
 
 
 def argon_six_species_physics(eq_system=NS, transport=CONSTANT, two_temperature=True, reactions=True,
@@ -784,6 +831,8 @@ def load():
     lib.tpsrhs_set_joule_heating.argtypes = [vp, C.c_void_p]
     lib.tpsrhs_set_reaction_rates.argtypes = [vp, C.c_void_p, C.c_int, C.c_int64]
     lib.tpsrhs_boltzmann_fields.argtypes = [vp, vp, C.c_int, vp]
+    lib.tpsrhs_lte_composition.argtypes = [vp, C.c_int64, vp, vp, vp]
+    lib.tpsrhs_species_from_lte.argtypes = [vp, C.POINTER(LteRestart), vp, vp, C.POINTER(LteRestartReport)]
     lib.tpsrhs_set_mixing_length.argtypes = [vp, C.c_void_p, C.POINTER(MixingLength)]
     lib.tpsrhs_face_tables.restype = C.c_int
     lib.tpsrhs_face_tables.argtypes = [C.POINTER(Mesh), C.c_int, C.POINTER(BC), vp, vp, vp, vp]
@@ -811,6 +860,7 @@ EXPORTED_SYMBOLS = [
     "tpsrhs_quadrature_points", "tpsrhs_integrate", "tpsrhs_nodal_stats", "tpsrhs_monitor_configure", "tpsrhs_monitor_read",
     "tpsrhs_visualization_layout", "tpsrhs_visualization_fields",
     "tpsrhs_set_reaction_rates", "tpsrhs_boltzmann_fields",
+    "tpsrhs_lte_composition", "tpsrhs_species_from_lte",
 ]
 
 

@@ -411,6 +411,37 @@ class RHSoperator:
             raise TpsRhsError(st, "tpsrhs_boltzmann_fields")
         return out
 
+    def lteComposition(self, T: torch.Tensor, p: torch.Tensor) -> torch.Tensor:
+        """``PerfectMixture::GetSpeciesFromLTE(T, p, n_sp)`` (``src/equation_of_state.cpp:2096-2187``): the equilibrium number
+        densities ``[num_species, n]`` in mol/m^3 at the temperatures ``T`` [K] and pressures ``p`` [Pa] (float64 device
+        tensors of ``n`` entries) -- Saha for the electrons, Boltzmann for the levels of the neutral.  Synchronous."""
+        for t in (T, p):
+            if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+                raise ValueError("expected contiguous one-dimensional float64 CUDA tensors")
+        if T.numel() != p.numel():
+            raise ValueError("T and p must have the same number of entries")
+        out = torch.empty((int(self._physics.mixture.num_species), T.numel()), dtype=torch.float64, device=self.device)
+        st = self._lib.tpsrhs_lte_composition(self._h, T.numel(), C.c_void_p(T.data_ptr()), C.c_void_p(p.data_ptr()),
+                                              C.c_void_p(out.data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_lte_composition")
+        return out
+
+    def speciesFromLTE(self, x: torch.Tensor, tables, want_primitives: bool = False):
+        """``M2ulPhyS::initilizeSpeciesFromLTE`` (``src/M2ulPhyS.cpp:2388-2461``, ``io/restartFromLTE = True``) and the species
+        clamp of ``Check_Undershoot``: ``x`` (the operator's state vector) holds rho, rho u, rho E of an LTE solution in its
+        rows ``0 .. nvel + 1``; every row is rewritten in place with the species state in equilibrium at the temperature and
+        pressure of the table gas.  ``tables``: a ``capi.LteRestart`` (``capi.make_lte_restart``).  Returns the
+        ``capi.LteRestartReport``, or ``(report, Up [num_equation, NDofs])`` with ``want_primitives``.  Synchronous."""
+        self._check(x)
+        up = torch.empty((self.num_equation, self.NDofs), dtype=torch.float64, device=self.device) if want_primitives else None
+        rep = capi.LteRestartReport()
+        st = self._lib.tpsrhs_species_from_lte(self._h, C.byref(tables), C.c_void_p(x.data_ptr()),
+                                               C.c_void_p(up.data_ptr()) if up is not None else None, C.byref(rep))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_species_from_lte")
+        return (rep, up) if want_primitives else rep
+
     def setMixingLength(self, distance, max_mixing_length=0.0, pr_ratio=1.0, lewis=1.0, bulk_multiplier=0.0):
         """``MixingLengthTransport`` (``src/mixing_length_transport.cpp``, ``[flow] useMixingLength``): ``distance`` =
         the wall-distance grid function, a float64 CUDA tensor of NDofs entries read at every ``Mult`` (kept alive
