@@ -854,6 +854,113 @@ int tpsrhs_monitor_configure(tpsrhs_handle h, int64_t interval, int64_t capacity
 int tpsrhs_monitor_read(tpsrhs_handle h, int64_t *nrecords, int64_t *ndropped, int64_t *iters_out, double *times_out,
                         double *dts_out, double *totals_out, double *mins_out, double *maxs_out, int reset);
 
+/* ---- surface integrals over boundary patches, and their history in the time loop --------------------------------------
+ * The reference integrates one thing over a boundary patch: its area, at start-up, for every inlet and outlet --
+ * BoundaryCondition::aggregateArea / aggregateBndryFaces (src/BoundaryCondition.cpp:59-92), printed by
+ * OutletBC::computeParallelArea (src/outletBC.cpp:329-343) and src/inletBC.cpp:306-307; the mass-flow outlets
+ * (TPSRHS_SUB_MF_NR / _PW) need it in data[7].  Here the same reduction takes any byNODES array: the area is the integral
+ * of ones, and the mass flow through a patch, the pressure and viscous force on a body and the heat load on a wall are
+ * integrals of arrays this library already has on the device (tpsrhs_get_primitives, tpsrhs_get_gradients,
+ * tpsrhs_eval_pointwise, tpsrhs_visualization_fields).  Those forces and loads are COMPOSITIONS THE REFERENCE DOES NOT
+ * HAVE; nothing of it is restated by them.  The library knows no physics here: it integrates what the caller hands it.
+ * The host selects the faces (tpsrhs_patch_faces, or any list of the caller's), the device computes.
+ * A FACE is (element, local face), local face = 2 d + s: reference direction d, side xi_d = s -- the slot convention of
+ * tpsrhs_face_tables.  Any element face may be in a set, also an interior one (a station plane inside the mesh).
+ * THE RULE, part of the contract:
+ *   - on face (d, s) the points are the tensor Gauss-Legendre points with NQ = p + 2 per tangential direction on
+ *     [0,1]^(dim-1); the tangential directions a < b are the other reference directions in ascending order, xi_d = s,
+ *     points numbered i + j*NQ (i along a);
+ *   - order-1 geometry, as for the samplers and the volume integrals: the bi-/trilinear map X through elem_coords;
+ *   - the area-weighted outward normal at a point is N_q = (2s - 1) sgn(det J) cof(J) e_d with cof(J) = det(J) J^{-T},
+ *     J = dX/dxi at the point (2-D, d = 0: (dy/dxi_1, -dx/dxi_1)); it is the normal of the sweeps and a polynomial of
+ *     degree <= 1 per tangential direction;
+ *   - dS_q = w_i w_j |N_q| and n dS = w_i w_j N_q (no square root in FLUX and NORMAL); with radial_weight != 0 every
+ *     weight is multiplied by r_q, the FIRST coordinate of the mapped point; there is no factor 2 pi;
+ *   - a nodal field is evaluated at the points with the operator's Lagrange basis (Gauss-Legendre or Gauss-Lobatto
+ *     nodes): the trace along d at xi_d = s first, then one tangential direction after the other.
+ * FLUX and NORMAL are exact for every f_h on every bilinear face (degree p + 1 <= 2p + 3 per direction).  SCALAR is exact
+ * on planar faces whose |N| is a polynomial (parallelograms, and planar faces in general up to the degree of the rule); on
+ * a warped face |N_q| is not a polynomial and SCALAR is a quadrature of it, not an exact integral.
+ * SUMMATION STRUCTURE, part of the contract: the terms of one face are summed first (a butterfly over its points).  The faces
+ * of a patch, sorted by (element, local face), are cut into fixed runs that never cross a patch boundary; a run is walked
+ * in batches of FB consecutive faces (FB = 64 / the power of two >= NQ^(dim-1)), and running sum k of the run collects the
+ * face sums k, k + FB, k + 2 FB, ... of the run in ascending order.  A last single-block kernel adds the running sums of a
+ * patch, taken in the order (run, k): lane t of one wave the entries t, t + 64, ... in ascending order, then a butterfly
+ * over the 64 lanes.  The order depends on the sorted face list and the order p alone.  No floating-point atomics: two calls
+ * on the same input give the same bits, and so do two surfaces made of the same faces in any input order.  With K_s = NQ^(dim-1) + nf_p + 8 dim (p+1) + 16, nf_p the faces of the
+ * patch, the rounding error of an output is at most K_s eps sum_q w_q G_q R_q A_q over the points of the patch, where
+ * G_q = |dX/da| |dX/db| (3-D; |dX/da| in 2-D) bounds |N_q|, R_q = |r_q| with the radial weight and 1 without, and
+ * A_q = sum_n |l_n(xi_q)| |f_n| (summed over the dim components for FLUX).  The terms of K_s: the butterfly over a face's
+ * points, the sums over the faces of the patch, the dim (p+1)-term interpolations with their products, and 16 for the
+ * geometry (the map, the cofactors, the weight).
+ * Partitioned meshes: every rank reduces its own faces and the caller combines the ranks, as with the volume integrals. */
+
+/* Host only, touches no device (next to tpsrhs_wall_faces): the boundary faces of `mesh` whose attribute is attributes[p],
+ * as elem_out, face_out (local face 2 d + s) and patch_out = p -- the faces aggregateBndryFaces
+ * (src/BoundaryCondition.cpp:76-92) counts per patch.  Ascending (element, local face) order, a boundary record matched to
+ * its owning element as tpsrhs_wall_faces matches it.  *num_faces_out is always the full count; min(count, capacity) faces
+ * are written, and the arrays may be NULL with capacity == 0.  An attribute without a face on this mesh gives an empty
+ * patch (on a partitioned mesh some ranks have none).  An attribute listed twice, num_attributes < 1, a boundary record
+ * that matches no element face, a NULL mesh, a dim other than 2 / 3, a negative capacity or a missing array:
+ * TPSRHS_ERR_INVALID_ARGUMENT. */
+int tpsrhs_patch_faces(const tpsrhs_mesh *mesh, int num_attributes, const int *attributes, int64_t capacity,
+                       int32_t *elem_out, int32_t *face_out, int32_t *patch_out, int64_t *num_faces_out);
+
+typedef struct tpsrhs_surface_s *tpsrhs_surface_handle;
+/* A set of num_faces faces in num_patches patches on the operator's mesh: what a BoundaryCondition of the reference holds
+ * of its patch once aggregateBndryFaces has run (src/BoundaryCondition.cpp:76-92: the faces of the attribute, their count),
+ * kept for the integrals instead of one number.  elem, face, patch: HOST arrays [num_faces]; the
+ * library sorts them by (patch, element, face) and keeps them on the device.  num_faces == 0 is legal (elem, face, patch
+ * may then be NULL): every integral of it is zero; so is a patch without faces.  A duplicate (element, face), an element
+ * outside 0 .. ne-1, a face outside 0 .. 2 dim - 1, a patch outside 0 .. num_patches-1, num_patches < 1, num_faces < 0 or
+ * a NULL handle / out: TPSRHS_ERR_INVALID_ARGUMENT before any device work.  The surface belongs to its operator, as a
+ * sampler does: tpsrhs_destroy frees the surfaces that are still alive, and their handles are dead afterwards. */
+int tpsrhs_surface_create(tpsrhs_handle h, int num_patches, int64_t num_faces, const int32_t *elem, const int32_t *face,
+                          const int32_t *patch, tpsrhs_surface_handle *out);
+/* No counterpart in the reference: what aggregateArea / aggregateBndryFaces fill (src/BoundaryCondition.cpp:59-92) lives
+ * as long as its BoundaryCondition; here the set can go before its operator.  NULL is a
+ * no-op.  A surface the patch history holds (tpsrhs_surface_monitor_configure) switches the history off first, records
+ * included -- the rule of tpsrhs_sampler_destroy for the sampler of the probes.  A handle that is no live surface -- destroyed
+ * already, or its operator destroyed -- is TPSRHS_ERR_INVALID_ARGUMENT here and in _info, _integrate and
+ * _monitor_configure: the library keeps a list of the live surfaces and reads nothing of a handle that is not on it. */
+int tpsrhs_surface_destroy(tpsrhs_surface_handle s);
+/* Any pointer may be NULL.  faces_per_patch[num_patches]: what aggregateBndryFaces counts (src/BoundaryCondition.cpp:76-92). */
+int tpsrhs_surface_info(tpsrhs_surface_handle s, int *num_patches, int64_t *num_faces, int64_t *faces_per_patch);
+enum tpsrhs_surface_form { TPSRHS_SURFACE_SCALAR = 0, TPSRHS_SURFACE_FLUX = 1, TPSRHS_SURFACE_NORMAL = 2 };
+/* field, out: DEVICE.  The value (row r, component c, node) is field[r*row_stride + c*comp_stride + node]; comp_stride is
+ * read by FLUX only.  Per patch p:
+ *   SCALAR  out[p*nrows + r]           = int f_r dS        (f = 1: aggregateArea, src/BoundaryCondition.cpp:59-74,
+ *                                                            the number computeParallelArea prints, src/outletBC.cpp:329-343)
+ *   FLUX    out[p*nrows + r]           = int F_r . n dS    F_r with dim components
+ *   NORMAL  out[(p*nrows + r)*dim + k] = int f_r n_k dS
+ * With row_stride = NDofs the arrays of tpsrhs_mult ([eq][NDofs]) go in as they are, and with row_stride = NDofs,
+ * comp_stride = neq*NDofs those of tpsrhs_get_gradients ([d][eq][NDofs]).  Asynchronous on the operator's stream; the
+ * field is read once; the scratch belongs to the surface.  nrows >= 1, no upper limit (rows are processed in passes).  A
+ * NULL surface, field or output, nrows < 1 or an unknown form: TPSRHS_ERR_INVALID_ARGUMENT before any device work. */
+int tpsrhs_surface_integrate(tpsrhs_surface_handle s, int form, int nrows, const double *field, int64_t row_stride,
+                             int64_t comp_stride, int radial_weight, double *out);
+
+/* Patch history inside the device time loop, the fourth observer beside statistics, probes and monitor: the history of
+ * what computeParallelArea (src/outletBC.cpp:329-343) computes once.  After every step of tpsrhs_advance /
+ * tpsrhs_advance_with a step counter goes up (this call zeroes it); when count % interval == 0 one record is enqueued
+ * between the steps:
+ *   iters[record]                      the count
+ *   times[record]                      the time, copied device-to-device from the loop's control block
+ *   integrals[record][patch][neq]      SCALAR of the rows of the new x
+ *   mass_flow[record][patch]           FLUX of the momentum rows 1 .. dim of x (comp_stride = NDofs)
+ * both with radial_weight = the operator's axisymmetric flag.  The semantics of tpsrhs_probe_configure and
+ * tpsrhs_monitor_configure: nothing returns to the host, a record is never part of the captured step graph and never
+ * causes a re-capture; when `capacity` records are held further records are dropped and counted, and nothing is written
+ * past the end; tpsrhs_step and tpsrhs_rk4_step neither count nor record.  s == NULL or interval == 0 switches the history
+ * off and frees its buffers; a surface of another operator, a negative interval, or capacity < 1 with the history on:
+ * TPSRHS_ERR_INVALID_ARGUMENT. */
+int tpsrhs_surface_monitor_configure(tpsrhs_handle h, tpsrhs_surface_handle s, int64_t interval, int64_t capacity);
+/* Copies the held records to HOST arrays and synchronises the stream.  Any pointer may be NULL.  reset != 0 starts the
+ * buffer again (records and dropped count) and leaves the step counter alone.  History not configured:
+ * TPSRHS_ERR_INVALID_ARGUMENT. */
+int tpsrhs_surface_monitor_read(tpsrhs_handle h, int64_t *nrecords, int64_t *ndropped, int64_t *iters_out, double *times_out,
+                                double *integrals_out, double *mass_flow_out, int reset);
+
 /* ---- plasma post-processing fields: M2ulPhyS::updateVisualizationVariables (src/M2ulPhyS.cpp:4156-4263, the fields it
  * registers at :1690-1787), which the reference has on the CPU only (its device build exits at :4157-4160) -------------
  * One DEVICE array out[nrows][NDofs], the rows in the reference's registration order (names as it writes them):

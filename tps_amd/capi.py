@@ -824,6 +824,13 @@ def load():
     lib.tpsrhs_nodal_stats.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     lib.tpsrhs_monitor_configure.argtypes = [vp, C.c_int64, C.c_int64]
     lib.tpsrhs_monitor_read.argtypes = [vp, _ip64, _ip64, vp, vp, vp, vp, vp, vp, C.c_int]
+    lib.tpsrhs_patch_faces.argtypes = [C.POINTER(Mesh), C.c_int, vp, C.c_int64, vp, vp, vp, _ip64]
+    lib.tpsrhs_surface_create.argtypes = [vp, C.c_int, C.c_int64, vp, vp, vp, C.POINTER(vp)]
+    lib.tpsrhs_surface_destroy.argtypes = [vp]
+    lib.tpsrhs_surface_info.argtypes = [vp, _ip32, _ip64, vp]
+    lib.tpsrhs_surface_integrate.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, C.c_int, vp]
+    lib.tpsrhs_surface_monitor_configure.argtypes = [vp, vp, C.c_int64, C.c_int64]
+    lib.tpsrhs_surface_monitor_read.argtypes = [vp, _ip64, _ip64, vp, vp, vp, vp, C.c_int]
     lib.tpsrhs_visualization_layout.argtypes = [C.POINTER(Physics), C.c_int, C.c_int, C.POINTER(VisLayout)]
     lib.tpsrhs_visualization_fields.argtypes = [vp, vp, vp]
     lib.tpsrhs_set_dt.argtypes = [vp, C.c_double]
@@ -858,6 +865,8 @@ EXPORTED_SYMBOLS = [
     "tpsrhs_sampler_create_device", "tpsrhs_node_coordinates", "tpsrhs_transfer", "tpsrhs_transfer_stats",
     "tpsrhs_wall_faces", "tpsrhs_wall_distance",
     "tpsrhs_quadrature_points", "tpsrhs_integrate", "tpsrhs_nodal_stats", "tpsrhs_monitor_configure", "tpsrhs_monitor_read",
+    "tpsrhs_patch_faces", "tpsrhs_surface_create", "tpsrhs_surface_destroy", "tpsrhs_surface_info", "tpsrhs_surface_integrate",
+    "tpsrhs_surface_monitor_configure", "tpsrhs_surface_monitor_read",
     "tpsrhs_visualization_layout", "tpsrhs_visualization_fields",
     "tpsrhs_set_reaction_rates", "tpsrhs_boltzmann_fields",
     "tpsrhs_lte_composition", "tpsrhs_species_from_lte",
@@ -916,6 +925,32 @@ def face_tables(host_mesh, bcs=()):
         raise RuntimeError(f"tpsrhs_face_tables: {lib.tpsrhs_status_string(st).decode()}: "
                            f"{lib.tpsrhs_last_error().decode()}")
     return fn.reshape(ne, nlf), fo.reshape(ne, nlf), ss[:ns], so[:ns]
+
+
+SURFACE_SCALAR, SURFACE_FLUX, SURFACE_NORMAL = 0, 1, 2  # enum tpsrhs_surface_form
+
+
+def patch_faces(host_mesh, attributes):
+    """Host-only call of ``tpsrhs_patch_faces``: ``(elem, face, patch)`` as int32 arrays -- the boundary faces of
+    ``host_mesh`` whose attribute is ``attributes[p]``, with ``patch = p`` and ``face = 2 d + s`` the owning element's
+    local face, in ascending (element, local face) order.  An attribute without a face gives an empty patch."""
+    lib = load()
+    ma = MeshArgs(host_mesh)
+    att = np.ascontiguousarray(attributes, dtype=np.int32).ravel()
+    n = C.c_int64(0)
+
+    def call(capacity, e, f, p):
+        st = lib.tpsrhs_patch_faces(C.byref(ma.c), int(att.size), att.ctypes.data if att.size else None, capacity,
+                                    e.ctypes.data if capacity else None, f.ctypes.data if capacity else None,
+                                    p.ctypes.data if capacity else None, C.byref(n))
+        if st != 0:
+            raise RuntimeError(f"tpsrhs_patch_faces: {lib.tpsrhs_status_string(st).decode()}: {lib.tpsrhs_last_error().decode()}")
+
+    call(0, None, None, None)  # the count
+    e, f, p = (np.zeros(n.value, dtype=np.int32) for _ in range(3))
+    if n.value:
+        call(n.value, e, f, p)
+    return e, f, p
 
 
 def wall_faces(host_mesh, bcs=(), attributes=None) -> np.ndarray:

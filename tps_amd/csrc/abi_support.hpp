@@ -32,6 +32,8 @@ tpsrhs::StepCadence *probe_cadence(tpsrhs_operator *h);    // sampling.hip
 void probe_record(tpsrhs_operator *h, const double *x);
 tpsrhs::StepCadence *monitor_cadence(tpsrhs_operator *h);  // integrals.hip
 void monitor_record(tpsrhs_operator *h, const double *x);
+tpsrhs::StepCadence *surface_cadence(tpsrhs_operator *h);  // surface.hip
+void surface_record(tpsrhs_operator *h, const double *x);
 
 // ---- sampling.hip
 // h is being destroyed: tpsrhs_transfer forgets it as a source and drops every cached sampler at its nodes (the cache is

@@ -58,9 +58,6 @@ struct QuadTab {
   double g[QUAD_MAXQ], w[QUAD_MAXQ];
 };
 
-constexpr int ipow(int b, int e) { return e == 0 ? 1 : b * ipow(b, e - 1); }
-constexpr int lanes_per_element(int n) { return n >= 64 ? 64 : (n <= 1 ? 1 : 2 * lanes_per_element((n + 1) / 2)); }
-
 template <int DIM, int P>
 struct IntegCfg {
   static constexpr int N1 = P + 1, NQ = P + 2;

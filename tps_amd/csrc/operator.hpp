@@ -33,6 +33,7 @@ const char *kKernelNames[NKERN] = {"k_traces", "k_gradient", "k_flux"};
 struct tpsrhs_stats_state;      // statistics.hpp: running mean and velocity covariances (statistics.hip)
 struct tpsrhs_sampling_state;   // sampling.hpp: point samplers and probe records (sampling.hip)
 struct tpsrhs_integrals_state;  // integrals.hpp: reduction scratch and monitor records (integrals.hip)
+struct tpsrhs_surface_state;    // surface.hpp: face sets of boundary patches and their history (surface.hip)
 // The owner of one of them: its type is complete in the one unit that creates it, which hands the deleter over with it
 // (this struct's inline destructor is compiled in every unit, the kernel families included).
 template <class T>
@@ -180,12 +181,14 @@ struct tpsrhs_operator {
   // sources, after the last k_flux launch of a Mult: launch.hpp) and tpsrhs_boltzmann_fields
   void (*ext_reactions)(tpsrhs_operator *, const double *, double *) = nullptr;
   void (*boltzmann_fields)(tpsrhs_operator *, const double *, int, double *) = nullptr;
-  // tpsrhs_stats_configure / tpsrhs_sampler_create, tpsrhs_probe_configure / tpsrhs_integrate, tpsrhs_monitor_configure;
+  // tpsrhs_stats_configure / tpsrhs_sampler_create, tpsrhs_probe_configure / tpsrhs_integrate, tpsrhs_monitor_configure /
+  // tpsrhs_surface_create, tpsrhs_surface_monitor_configure;
   // NULL: none yet.  Last, and reset first in the destructor: they go while the events and the second stream still exist.
   // Whoever lets one go while its kernels may still run synchronises the stream first (tpsrhs_destroy, the configure calls).
   OwnedState<tpsrhs_stats_state> stats{nullptr, nullptr};
   OwnedState<tpsrhs_sampling_state> sampling{nullptr, nullptr};
   OwnedState<tpsrhs_integrals_state> integrals{nullptr, nullptr};
+  OwnedState<tpsrhs_surface_state> surface{nullptr, nullptr};
 
   MeshDev mesh_dev() const {
     MeshDev m;
@@ -206,6 +209,7 @@ struct tpsrhs_operator {
     stats.reset();
     sampling.reset();
     integrals.reset();
+    surface.reset();
     for (auto &e : ev_halo)
       if (e) (void)hipEventDestroy(e);
     if (comm_stream) (void)hipStreamDestroy(comm_stream);

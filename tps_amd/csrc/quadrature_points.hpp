@@ -31,6 +31,11 @@ constexpr int QUAD_MAXQ = TPSRHS_MAXORDER + 2;  // 7 points per direction at p =
 
 inline int quad_points_1d(int order) { return order + 2; }
 
+// for the reduction kernels (integrals.hpp, surface.hpp): b^e, and the power of two >= n, at most 64 -- the lanes of a wave
+// that share one element or face
+constexpr int ipow(int b, int e) { return e == 0 ? 1 : b * ipow(b, e - 1); }
+constexpr int lanes_per_element(int n) { return n >= 64 ? 64 : (n <= 1 ? 1 : 2 * lanes_per_element((n + 1) / 2)); }
+
 // x(xi) and det dx/dxi of one element; v: [2^DIM][DIM], lexicographic corners
 template <int DIM>
 TPSRHS_HOST_DEVICE inline void quad_geometry(const double *v, const double *xi, double *x, double *det) {

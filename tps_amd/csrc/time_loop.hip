@@ -140,16 +140,17 @@ void step_stages(tpsrhs_operator *h, int integrator, double *x, double dt, const
 }
 
 // What the time loop does between two steps, and whether any of it falls after the first of the next two: everything that
-// reads x between steps goes through these two, so that the loop itself knows nothing about statistics, probes or the
-// monitor.  Each observer has one StepCadence (record_log.hpp; interval 0: off), which answers both questions.
+// reads x between steps goes through these two, so that the loop itself knows nothing about statistics, probes, the
+// monitor or the patch history.  Each observer has one StepCadence (record_log.hpp; interval 0: off), which answers both questions.
 void after_step(tpsrhs_operator *h, const double *x) {
   if (StepCadence *c = stats_cadence(h); c && c->tick()) stats_sample(h, x);
   if (StepCadence *c = probe_cadence(h); c && c->tick()) probe_record(h, x);
   if (StepCadence *c = monitor_cadence(h); c && c->tick()) monitor_record(h, x);
+  if (StepCadence *c = surface_cadence(h); c && c->tick()) surface_record(h, x);
 }
 bool work_due_after_next(tpsrhs_operator *h) {
-  const StepCadence *s = stats_cadence(h), *p = probe_cadence(h), *m = monitor_cadence(h);
-  return (s && s->due_after_next()) || (p && p->due_after_next()) || (m && m->due_after_next());
+  const StepCadence *s = stats_cadence(h), *p = probe_cadence(h), *m = monitor_cadence(h), *f = surface_cadence(h);
+  return (s && s->due_after_next()) || (p && p->due_after_next()) || (m && m->due_after_next()) || (f && f->due_after_next());
 }
 
 int step_with(tpsrhs_handle h, int integrator, const char *who, double *x, double *time, double dt, double *max_char_speed,

@@ -42,6 +42,14 @@ int tpsrhs_wall_faces(const tpsrhs_mesh *mesh, int num_bcs, const tpsrhs_bc *bcs
   return st;
 }
 
+int tpsrhs_patch_faces(const tpsrhs_mesh *mesh, int num_attributes, const int *attributes, int64_t capacity, int32_t *elem_out,
+                       int32_t *face_out, int32_t *patch_out, int64_t *num_faces_out) {
+  const int st = patch_faces(mesh, num_attributes, attributes, capacity, elem_out, face_out, patch_out, num_faces_out);
+  if (st != TPSRHS_OK)
+    return fail(st, "tpsrhs_patch_faces: needs a mesh of dim 2 or 3 whose boundary records are faces of its elements, num_attributes >= 1 distinct attributes, capacity >= 0 with its arrays, and num_faces_out");
+  return st;
+}
+
 int tpsrhs_wall_distance(tpsrhs_handle h, int64_t num_faces, const double *face_xyz, double *distance_out) {
   if (!h || !distance_out || num_faces < 0 || (num_faces > 0 && !face_xyz))
     return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_wall_distance: needs a handle, num_faces >= 0, the faces and the output array");

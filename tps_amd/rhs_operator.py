@@ -552,6 +552,62 @@ class RHSoperator:
         return dict(iters=iters[:n].copy(), times=times[:n].copy(), dts=dts[:n].copy(), totals=totals[:n].copy(),
                     mins=mins[:n].copy(), maxs=maxs[:n].copy(), ndropped=ndrop.value)
 
+    # -- surface integrals over boundary patches and their history -----------------------------------------------------------
+    def createSurface(self, attributes=None, faces=None) -> "Surface":
+        """A set of element faces in patches (``tpsrhs_surface_create``).  ``attributes``: the boundary attributes of the
+        operator's mesh, one patch each (:func:`tps_amd.capi.patch_faces` -- the faces
+        ``BoundaryCondition::aggregateBndryFaces`` counts, ``src/BoundaryCondition.cpp:76-92``).  ``faces``: an explicit
+        ``(elem, face, patch)`` triple of integer arrays, ``face = 2 d + s``; any element face may be listed, also an
+        interior one; the number of patches is ``max(patch) + 1``, or ``(elem, face, patch, num_patches)``.
+        The operator owns the surface: closing the operator closes it."""
+        if (attributes is None) == (faces is None):
+            raise ValueError("give either the boundary attributes or the faces")
+        if attributes is not None:
+            attributes = np.ascontiguousarray(attributes, dtype=np.int32).ravel()
+            elem, face, patch = capi.patch_faces(self._mesh, attributes)
+            npatch = int(attributes.size)
+        else:
+            elem, face, patch = (np.ascontiguousarray(a, dtype=np.int32).ravel() for a in faces[:3])
+            npatch = int(faces[3]) if len(faces) > 3 else (int(patch.max()) + 1 if patch.size else 1)
+            if not (elem.size == face.size == patch.size):
+                raise ValueError("elem, face and patch must have the same length")
+        s = Surface(self, npatch, elem, face, patch)
+        self._surfaces = [w for w in getattr(self, "_surfaces", []) if w() is not None] + [weakref.ref(s)]
+        return s
+
+    def surfaceMonitor(self, surface, interval: int, capacity: int):
+        """Patch history inside :meth:`advance`: after every step a counter goes up (zeroed here), and when it is a
+        multiple of ``interval`` the count, the device-side time, the integrals of the conserved state over every patch of
+        ``surface`` and the mass flow through it are appended to a device buffer of ``capacity`` records; further records
+        are dropped and counted.  ``surface=None`` or ``interval=0`` switches the history off."""
+        st = self._lib.tpsrhs_surface_monitor_configure(self._h, surface._s if surface is not None else None, int(interval),
+                                                        int(capacity))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_surface_monitor_configure")
+        # (a weak reference: the operator does not keep the surface alive, and the two form no cycle)
+        self._surface_monitor = ((weakref.ref(surface), surface.num_patches, int(capacity))
+                                 if surface is not None and interval != 0 else None)
+
+    def readSurfaceMonitor(self, reset: bool = False):
+        """``dict(iters (nrec,), times (nrec,), integrals (nrec, npatch, num_equation), mass_flow (nrec, npatch), ndropped)``
+        as numpy arrays; synchronises.  ``reset`` starts the buffer again and leaves the step counter alone."""
+        if getattr(self, "_surface_monitor", None) is None:
+            raise TpsRhsError(self._lib.tpsrhs_surface_monitor_read(self._h, None, None, None, None, None, None, 0),
+                              "tpsrhs_surface_monitor_read")
+        _, npatch, capacity = self._surface_monitor
+        iters = np.zeros(capacity, dtype=np.int64)
+        times = np.zeros(capacity)
+        integrals = np.zeros((capacity, npatch, self.num_equation))
+        mass_flow = np.zeros((capacity, npatch))
+        nrec, ndrop = C.c_int64(0), C.c_int64(0)
+        st = self._lib.tpsrhs_surface_monitor_read(self._h, C.byref(nrec), C.byref(ndrop), iters.ctypes.data, times.ctypes.data,
+                                                   integrals.ctypes.data, mass_flow.ctypes.data, 1 if reset else 0)
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_surface_monitor_read")
+        n = nrec.value
+        return dict(iters=iters[:n].copy(), times=times[:n].copy(), integrals=integrals[:n].copy(),
+                    mass_flow=mass_flow[:n].copy(), ndropped=ndrop.value)
+
     def kernel_bytes(self):
         names = (C.c_char_p * 8)()
         b = (C.c_double * 8)()
@@ -567,7 +623,11 @@ class RHSoperator:
             for w in getattr(self, "_samplers", []):  # tpsrhs_destroy frees them: their handles die here
                 if w() is not None:
                     w()._s = None
+            for w in getattr(self, "_surfaces", []):
+                if w() is not None:
+                    w()._s = None
             self._probe = None
+            self._surface_monitor = None
             self._lib.tpsrhs_destroy(self._h)
             self._h = None
 
@@ -637,6 +697,88 @@ class PointSampler:
             if getattr(self._op, "_probe", None) is not None and self._op._probe[0] is self:
                 self._op._probe = None
             self._lib.tpsrhs_sampler_destroy(self._s)
+        self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Surface:
+    """A set of element faces in patches on one operator's mesh (``tpsrhs_surface_*``): what the reference aggregates per
+    inlet and outlet at start-up (``BoundaryCondition::aggregateArea`` / ``aggregateBndryFaces``,
+    ``src/BoundaryCondition.cpp:59-92``), with the integrals of any byNODES array over it."""
+
+    _FORMS = {"scalar": capi.SURFACE_SCALAR, "flux": capi.SURFACE_FLUX, "normal": capi.SURFACE_NORMAL}
+
+    def __init__(self, op: RHSoperator, num_patches: int, elem, face, patch):
+        self._lib = capi.load()
+        self._op = op
+        self.num_patches = int(num_patches)
+        s = C.c_void_p()
+        n = int(elem.size)
+        st = self._lib.tpsrhs_surface_create(op._h, self.num_patches, n, elem.ctypes.data if n else None,
+                                             face.ctypes.data if n else None, patch.ctypes.data if n else None, C.byref(s))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_surface_create")
+        self._s = s
+
+    def info(self):
+        """``(num_patches, num_faces, faces_per_patch (num_patches,))``."""
+        np_, nf = C.c_int(0), C.c_int64(0)
+        per = np.zeros(self.num_patches, dtype=np.int64)
+        st = self._lib.tpsrhs_surface_info(self._s, C.byref(np_), C.byref(nf), per.ctypes.data)
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_surface_info")
+        return np_.value, nf.value, per
+
+    def integrate(self, field: torch.Tensor, form: str = "scalar", radial=None, row_stride=None, comp_stride=None) -> torch.Tensor:
+        """The integrals of ``field`` over every patch, a new CUDA tensor: ``"scalar"`` -> ``(npatch, nrows)`` of
+        ``int f dS``; ``"flux"`` -> ``(npatch, nrows)`` of ``int F . n dS``; ``"normal"`` -> ``(npatch, nrows, dim)`` of
+        ``int f n dS``.  The value (row r, component c, node) is ``field.flatten()[r*row_stride + c*comp_stride + node]``.
+        Defaults: ``row_stride = NDofs`` for scalar and normal; for flux ``field`` is ``[nrows][dim][NDofs]``
+        (``row_stride = dim*NDofs``, ``comp_stride = NDofs``).  With explicit strides the number of rows is what fits into
+        ``field``.  ``radial``: weight every point by its first coordinate (``None``: the operator's axisymmetric flag).
+        Asynchronous on the operator's stream."""
+        op = self._op
+        if form not in self._FORMS:
+            raise ValueError("form is one of 'scalar', 'flux', 'normal'")
+        if field.dtype != torch.float64 or not field.is_cuda or not field.is_contiguous() or not field.numel():
+            raise ValueError("expected a contiguous float64 CUDA tensor")
+        n, dim = op.NDofs, op.dim
+        ncomp = dim if form == "flux" else 1
+        if comp_stride is None:
+            comp_stride = n
+        if row_stride is None:
+            row_stride = ncomp * n
+        # the rows whose last value still lies inside the field
+        span = (ncomp - 1) * int(comp_stride) + n
+        if field.numel() < span:
+            raise ValueError("the field is shorter than one row")
+        nrows = (field.numel() - span) // int(row_stride) + 1 if row_stride > 0 else 1
+        if radial is None:
+            radial = bool(op._disc.axisymmetric)
+        shape = (self.num_patches, nrows, dim) if form == "normal" else (self.num_patches, nrows)
+        out = torch.empty(shape, dtype=torch.float64, device=field.device)
+        st = self._lib.tpsrhs_surface_integrate(self._s, self._FORMS[form], nrows, C.c_void_p(field.data_ptr()), int(row_stride),
+                                                int(comp_stride), 1 if radial else 0, C.c_void_p(out.data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_surface_integrate")
+        return out
+
+    def area(self, radial=None) -> torch.Tensor:
+        """``(npatch,)``: the scalar integral of ones -- ``BoundaryCondition::aggregateArea``
+        (``src/BoundaryCondition.cpp:59-74``), the ``data[7]`` of the mass-flow outlets."""
+        ones = torch.ones(self._op.NDofs, dtype=torch.float64, device=self._op.device)
+        return self.integrate(ones, "scalar", radial=radial)[:, 0]
+
+    def close(self):
+        if getattr(self, "_s", None):
+            if getattr(self._op, "_surface_monitor", None) is not None and self._op._surface_monitor[0]() is self:
+                self._op._surface_monitor = None
+            self._lib.tpsrhs_surface_destroy(self._s)
         self._s = None
 
     def __del__(self):
