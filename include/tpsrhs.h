@@ -961,6 +961,45 @@ int tpsrhs_surface_monitor_configure(tpsrhs_handle h, tpsrhs_surface_handle s, i
 int tpsrhs_surface_monitor_read(tpsrhs_handle h, int64_t *nrecords, int64_t *ndropped, int64_t *iters_out, double *times_out,
                                 double *integrals_out, double *mass_flow_out, int reset);
 
+/* ---- the nodal flux tensor of RHSoperator::GetFlux (src/rhs_operator.cpp:493-559) and the loads on a patch ---------------
+ * The third array RHSoperator::Mult works from, beside the primitives and their gradients: per node
+ *   CONVECTIVE  Fluxes::ComputeConvectiveFluxes(state)                              src/fluxes.cpp:135-170
+ *   VISCOUS     Fluxes::ComputeViscousFluxes(state, gradUp, xyz, delta, dist)       src/fluxes.cpp:178-335, with ITS sign;
+ *               zero for TPSRHS_EULER
+ *   TOTAL       CONVECTIVE - VISCOUS, the flux(i, d, k) of GetFlux (:532-541)
+ * x, out: DEVICE.  out[d][eq][node], dim * neq * NDofs doubles: the layout of tpsrhs_get_gradients, so it goes into
+ * tpsrhs_surface_integrate(FLUX) with row_stride = NDofs, comp_stride = neq*NDofs and into tpsrhs_sample as it is.  In the
+ * axisymmetric formulation dim = 2 and the rows include the swirl momentum, as in GetFlux.
+ * The state is x with the species rows clamped at zero (:512-517); gradUp is the operator's; xyz is the node's position on
+ * the order-1 map; delta is elSize (:154); dist is the distance array of tpsrhs_set_mixing_length when one is set; the
+ * radius goes to the axisymmetric and table-gas closures: every closure gets the context the flux sweep of tpsrhs_mult
+ * gives it, sub-grid scale models, viscous sponge and mixing length included.
+ * gradients_current == 0: the call first runs what tpsrhs_update_gradients(h, x) runs (as tpsrhs_visualization_fields
+ * does), then the pass.  gradients_current != 0: the caller asserts that Up / gradUp of x are held (after tpsrhs_mult(x)
+ * or tpsrhs_update_gradients(x)); the pass alone runs.
+ * NUMERICAL RULES, part of the contract: VISCOUS is evaluated from the closure's own terms, never as a difference of the
+ * other two (on a wall F_v is many orders below F_c); TOTAL is formed from the two parts by ONE subtraction per entry.
+ * The eight Coulomb collision fits of the argon-minimal transport are evaluated from their FORMULAS here; the flux sweep of
+ * the 3-D p = 3 ternary kernels reads them from a polynomial table, so TOTAL differs from what that
+ * sweep contracts by the table's documented error (tps_amd/csrc/coulomb_table.hpp: rounding of one Horner chain per fit,
+ * measured by tests/test_coulomb_table.py) -- and is comparable with the CPU oracle.
+ * Asynchronous on the operator's stream.  The pass reads nothing but x, gradUp and the mesh and writes nothing but out: a
+ * later tpsrhs_mult gives the bits it would have given.  Every gas model, formulation, basis pair and order an operator
+ * exists for is served.  NULL h, x or out, or an unknown part: TPSRHS_ERR_INVALID_ARGUMENT before any device work. */
+enum tpsrhs_flux_part { TPSRHS_FLUX_TOTAL = 0, TPSRHS_FLUX_CONVECTIVE = 1, TPSRHS_FLUX_VISCOUS = 2 };
+int tpsrhs_get_flux(tpsrhs_handle h, const double *x, int part, int gradients_current, double *out);
+/* out[patch][neq] (DEVICE) = int F_part . n dS per patch: tpsrhs_get_flux into a scratch of dim*neq*NDofs doubles that
+ * belongs to the surface (allocated at the first call, freed with the surface), then the FLUX reduction of
+ * tpsrhs_surface_integrate with radial_weight = the operator's axisymmetric flag -- its rule, summation structure, error
+ * bound and determinism.  A COMPOSITION THE REFERENCE DOES NOT HAVE.  n points out of the element: on a wall patch the
+ * momentum rows of TOTAL are the force the fluid exerts on the wall, pressure and viscous, and the energy row is the power
+ * leaving the fluid through the patch (VISCOUS alone: minus the viscous force, minus the conducted and diffused power).
+ * F is the flux of the INTERIOR trace extrapolated with the operator's basis, NOT the numerical boundary flux of the
+ * boundary-condition classes; the two agree to the order of the scheme.  Partitioned meshes: each rank reduces its own
+ * faces and the caller adds.  A handle that is no live surface, a NULL x or out, an unknown part:
+ * TPSRHS_ERR_INVALID_ARGUMENT before any device work. */
+int tpsrhs_surface_loads(tpsrhs_surface_handle s, const double *x, int part, int gradients_current, double *out);
+
 /* ---- plasma post-processing fields: M2ulPhyS::updateVisualizationVariables (src/M2ulPhyS.cpp:4156-4263, the fields it
  * registers at :1690-1787), which the reference has on the CPU only (its device build exits at :4157-4160) -------------
  * One DEVICE array out[nrows][NDofs], the rows in the reference's registration order (names as it writes them):

@@ -831,6 +831,8 @@ def load():
     lib.tpsrhs_surface_integrate.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, C.c_int, vp]
     lib.tpsrhs_surface_monitor_configure.argtypes = [vp, vp, C.c_int64, C.c_int64]
     lib.tpsrhs_surface_monitor_read.argtypes = [vp, _ip64, _ip64, vp, vp, vp, vp, C.c_int]
+    lib.tpsrhs_get_flux.argtypes = [vp, vp, C.c_int, C.c_int, vp]
+    lib.tpsrhs_surface_loads.argtypes = [vp, vp, C.c_int, C.c_int, vp]
     lib.tpsrhs_visualization_layout.argtypes = [C.POINTER(Physics), C.c_int, C.c_int, C.POINTER(VisLayout)]
     lib.tpsrhs_visualization_fields.argtypes = [vp, vp, vp]
     lib.tpsrhs_set_dt.argtypes = [vp, C.c_double]
@@ -867,6 +869,7 @@ EXPORTED_SYMBOLS = [
     "tpsrhs_quadrature_points", "tpsrhs_integrate", "tpsrhs_nodal_stats", "tpsrhs_monitor_configure", "tpsrhs_monitor_read",
     "tpsrhs_patch_faces", "tpsrhs_surface_create", "tpsrhs_surface_destroy", "tpsrhs_surface_info", "tpsrhs_surface_integrate",
     "tpsrhs_surface_monitor_configure", "tpsrhs_surface_monitor_read",
+    "tpsrhs_get_flux", "tpsrhs_surface_loads",
     "tpsrhs_visualization_layout", "tpsrhs_visualization_fields",
     "tpsrhs_set_reaction_rates", "tpsrhs_boltzmann_fields",
     "tpsrhs_lte_composition", "tpsrhs_species_from_lte",
@@ -928,6 +931,18 @@ def face_tables(host_mesh, bcs=()):
 
 
 SURFACE_SCALAR, SURFACE_FLUX, SURFACE_NORMAL = 0, 1, 2  # enum tpsrhs_surface_form
+FLUX_TOTAL, FLUX_CONVECTIVE, FLUX_VISCOUS = 0, 1, 2  # enum tpsrhs_flux_part
+_FLUX_PARTS = {"total": FLUX_TOTAL, "convective": FLUX_CONVECTIVE, "viscous": FLUX_VISCOUS}
+
+
+def flux_part(part) -> int:
+    """``"total"`` / ``"convective"`` / ``"viscous"`` -> ``enum tpsrhs_flux_part``; an integer passes as it is (the library
+    refuses an unknown one)."""
+    if isinstance(part, str):
+        if part not in _FLUX_PARTS:
+            raise ValueError("part is one of 'total', 'convective', 'viscous'")
+        return _FLUX_PARTS[part]
+    return int(part)
 
 
 def patch_faces(host_mesh, attributes):

@@ -23,6 +23,11 @@ const std::vector<double> &coulomb_table_host();
 // external_rates.hip), loaded on demand; `who` starts the message of a refusal
 void load_plasma_vis_family(tpsrhs_operator *h, const char *who);
 
+// ---- flux_fields.hip
+// the pass of tpsrhs_get_flux on the operator's stream, after tpsrhs_update_gradients' work unless the caller holds Up / gradUp
+// of x (tpsrhs_surface_loads composes it with the FLUX reduction)
+void get_flux(tpsrhs_operator *h, const double *x, int part, int gradients_current, double *out);
+
 // ---- the observers of the device time loop (time_loop.hip: after_step / work_due_after_next).  The loop knows each by its
 // StepCadence (record_log.hpp; NULL: not configured, interval 0: off) and by the function that does its work on the
 // operator's stream once the cadence says so.

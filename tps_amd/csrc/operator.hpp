@@ -217,6 +217,10 @@ struct tpsrhs_operator {
       for (auto &e : set)
         if (e) (void)hipEventDestroy(e);
   }
+  // tpsrhs_get_flux (flux_fields.hpp): the pass of a plasma family, set with vis_fields from the same shared object; NULL for
+  // every other physics, whose passes live in flux_fields.hip.  (part, x, out) on the operator's stream.  Last member: the
+  // layout of everything before it is what the units of the sweeps were compiled with.
+  void (*flux_fields)(tpsrhs_operator *, int, const double *, double *) = nullptr;
 };
 
 #endif

@@ -12,6 +12,7 @@
 #define TPSRHS_PLASMA_VIS_FAMILY_HPP_
 
 #include "external_rates.hpp"
+#include "flux_fields.hpp"
 #include "launch.hpp"
 #include "physics_plasma.hpp"
 
@@ -21,6 +22,8 @@ static void pick_plasma_vis_of(tpsrhs_operator *op) {
   // the per-node passes of the Boltzmann coupling (external_rates.hpp) need the same closures and live here for the same reason
   op->ext_reactions = &launch_external_reactions<PlasmaPhys<DIM, NVEL, NSP, AMBI, TWOT, TR>>;
   op->boltzmann_fields = &launch_boltzmann_fields<PlasmaPhys<DIM, NVEL, NSP, AMBI, TWOT, TR>>;
+  // ... and the nodal flux tensor of tpsrhs_get_flux (flux_fields.hpp)
+  op->flux_fields = &launch_flux_fields<PlasmaPhys<DIM, NVEL, NSP, AMBI, TWOT, TR>>;
 }
 
 // the transport models a family instantiates: those of plasma_family.hpp::pick_plasma_family

@@ -216,6 +216,21 @@ int tpsrhs_surface_integrate(tpsrhs_surface_handle s, int form, int nrows, const
   });
 }
 
+int tpsrhs_surface_loads(tpsrhs_surface_handle s, const double *x, int part, int gradients_current, double *out) {
+  if (!s || !x || !out) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_surface_loads: needs a surface, the device state and the device output");
+  if (!surface_alive(s)) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_surface_loads: not a surface of a live operator");
+  if (part != TPSRHS_FLUX_TOTAL && part != TPSRHS_FLUX_CONVECTIVE && part != TPSRHS_FLUX_VISCOUS)
+    return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_surface_loads: part " + std::to_string(part) + " is none of TOTAL, CONVECTIVE, VISCOUS");
+  tpsrhs_operator *h = s->owner;
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(h->device));
+    if (!s->d_flux) s->d_flux = DevBuf<double>(static_cast<size_t>(h->dim) * h->neq * h->ndofs);
+    get_flux(h, x, part, gradients_current, s->d_flux.get());  // [d][eq][NDofs]: rows eq, components d
+    integrate_surface(h, s, TPSRHS_SURFACE_FLUX, h->neq, s->d_flux.get(), h->ndofs, static_cast<int64_t>(h->neq) * h->ndofs,
+                      (h->dim == 2 && h->nvel == 3) ? 1 : 0, out);
+  });
+}
+
 int tpsrhs_surface_monitor_configure(tpsrhs_handle h, tpsrhs_surface_handle s, int64_t interval, int64_t capacity) {
   if (!h) return fail(TPSRHS_ERR_INVALID_ARGUMENT, "tpsrhs_surface_monitor_configure: NULL handle");
   if (interval < 0 || capacity < 0)

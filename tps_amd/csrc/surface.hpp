@@ -62,6 +62,7 @@ struct tpsrhs_surface_s {
   DevBuf<SurfaceRun> d_runs;        // [nblocks]
   DevBuf<int32_t> d_patch_block;    // [num_patches + 1] the first block of every patch
   DevBuf<double> d_partial;         // [SURF_ACC][nblocks * fb]
+  DevBuf<double> d_flux;            // [dim][neq][NDofs]: the tensor of tpsrhs_surface_loads, allocated at its first call
 };
 
 // the patch history (tpsrhs_surface_monitor_configure); surface NULL: off

@@ -115,6 +115,20 @@ class RHSoperator:
             raise TpsRhsError(st, "tpsrhs_get_gradients")
         return out.view(self.dim, self.num_equation, self.NDofs)
 
+    def getFlux(self, x: torch.Tensor, part: str = "total", gradients_current: bool = False) -> torch.Tensor:
+        """The nodal flux tensor of ``RHSoperator::GetFlux`` (``src/rhs_operator.cpp:493-559``) at the state ``x``:
+        ``[dim, num_equation, NDofs]``, the layout of :meth:`getGradients`.  ``part``: ``"convective"``
+        (``ComputeConvectiveFluxes``), ``"viscous"`` (``ComputeViscousFluxes``, its sign) or ``"total"`` (their difference).
+        ``Up`` and ``gradUp`` of the operator are refreshed from ``x`` first unless ``gradients_current`` (the caller has
+        just run ``Mult(x)`` or ``updateGradients(x)``).  Asynchronous on the operator's stream."""
+        self._check(x)
+        out = torch.empty((self.dim, self.num_equation, self.NDofs), dtype=torch.float64, device=self.device)
+        st = self._lib.tpsrhs_get_flux(self._h, C.c_void_p(x.data_ptr()), capi.flux_part(part), 1 if gradients_current else 0,
+                                       C.c_void_p(out.data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_get_flux")
+        return out
+
     def getPlasmaConductivity(self, x: torch.Tensor) -> torch.Tensor:
         """``plasma_conductivity_`` of ``SourceTerm`` (``src/source_term.cpp:125-199``): sigma at the nodes of the state
         ``x`` -- what the EM solver of the coupled torch runs reads (mixtures and the table gas)."""
@@ -766,6 +780,20 @@ class Surface:
                                                 int(comp_stride), 1 if radial else 0, C.c_void_p(out.data_ptr()))
         if st != 0:
             raise TpsRhsError(st, "tpsrhs_surface_integrate")
+        return out
+
+    def loads(self, x: torch.Tensor, part: str = "total", gradients_current: bool = False) -> torch.Tensor:
+        """``(npatch, num_equation)``: ``int F_part . n dS`` per patch of the nodal flux tensor of the state ``x``
+        (:meth:`RHSoperator.getFlux` followed by the flux reduction, ``tpsrhs_surface_loads``).  ``n`` points out of the
+        element: on a wall patch the momentum rows of ``"total"`` are the force the fluid exerts on the wall, the energy row
+        the power leaving the fluid.  The flux is that of the interior trace, not the numerical boundary flux."""
+        op = self._op
+        op._check(x)
+        out = torch.empty((self.num_patches, op.num_equation), dtype=torch.float64, device=op.device)
+        st = self._lib.tpsrhs_surface_loads(self._s, C.c_void_p(x.data_ptr()), capi.flux_part(part), 1 if gradients_current else 0,
+                                            C.c_void_p(out.data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_surface_loads")
         return out
 
     def area(self, radial=None) -> torch.Tensor:
