@@ -673,6 +673,32 @@ int tpsrhs_probe_read(tpsrhs_handle h, int64_t *nrecords, int64_t *ndropped, int
  * by dt in EVERY Mult (src/outletBC.cpp:712-724).  tpsrhs_rk4_step sets it itself. */
 int tpsrhs_set_dt(tpsrhs_handle h, double dt);
 
+/* ---- fields on a refined element lattice: what a ParaView output step evaluates ------------------------------------------
+ * The reference's time loop and its visualization mode end in paraviewColl->Save() (src/M2ulPhyS.cpp:443-446, 1877-1906,
+ * 2043-2045, 4131-4133): a ParaViewDataCollection with SetLevelsOfDetail(order), for which MFEM evaluates every registered
+ * grid function at a closed uniform lattice of each element (GridFunction::GetValues at the points of a RefinedGeometry).
+ * The conventions are those of the sampling section above (basis, local numbering, order-1 geometry), and in addition:
+ *   - for levels = L, 1 <= L <= TPSRHS_MAXLATTICE, every element carries the lattice t_a = a / L, a = 0..L, per direction;
+ *     local = a + b*(L+1) + c*(L+1)^2; point index = e*(L+1)^dim + local; npts = num_elements*(L+1)^dim;
+ *   - arrays are [row][npts];
+ *   - a point on a face shared by two elements exists once PER ELEMENT and carries that element's own polynomial (the
+ *     sampler lets the lowest-index element answer there; a DG picture needs both values).
+ * The evaluation is a sum-factorised contraction of an element's nodal tile with the 1-D matrix B[a][i] = l_i(a / L)
+ * (k_lattice, lattice.hpp): dim*(p+1) multiply-adds per value, the field read once, no location records.  B is formed on
+ * the host in double at every call from the operator's own nodes; the entries keep no state on the operator.
+ * All three are asynchronous on the operator's stream except tpsrhs_lattice_size, which touches no device.  A NULL
+ * argument, nrows < 1 or levels outside 1..TPSRHS_MAXLATTICE: TPSRHS_ERR_INVALID_ARGUMENT before any device work. */
+#define TPSRHS_MAXLATTICE 8
+/* points_per_element = (levels+1)^dim, npts = num_elements * points_per_element.  Host only. */
+int tpsrhs_lattice_size(tpsrhs_handle h, int levels, int64_t *points_per_element, int64_t *npts);
+/* xyz_out: DEVICE [dim][npts], the bi-/trilinear vertex map at the lattice points.  The shape weights are products of t
+ * and 1 - t (as in tpsrhs_node_coordinates), so a lattice corner is the element's vertex bit for bit. */
+int tpsrhs_lattice_coordinates(tpsrhs_handle h, int levels, double *xyz_out);
+/* field: DEVICE [nrows][NDofs], any byNODES array; out: DEVICE [nrows][npts], doubles, or with out_float32 != 0 floats:
+ * the double result converted once, round to nearest (ParaView files are normally single precision, and the copy to the
+ * host is the expensive part of an output step).  nrows >= 1, no upper limit. */
+int tpsrhs_lattice_fields(tpsrhs_handle h, int levels, int nrows, const double *field, void *out, int out_float32);
+
 /* ---- next row of the scope table: the other ForcingTerms of RHSoperator ----
  * RHSoperator appends these to its `forcing` array (src/rhs_operator.cpp:101-166) and adds them to y
  * after the inverse mass (src/rhs_operator.cpp:451-461).  SourceTerm and AxisymmetricSource follow from

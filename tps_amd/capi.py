@@ -814,6 +814,9 @@ def load():
     lib.tpsrhs_sampler_create_device.argtypes = [vp, C.c_int64, vp, C.c_double, C.c_double, C.POINTER(vp)]
     lib.tpsrhs_node_coordinates.argtypes = [vp, vp]
     lib.tpsrhs_transfer.argtypes = [vp, vp, C.c_int, vp, vp, C.c_double, C.c_double, _ip64]
+    lib.tpsrhs_lattice_size.argtypes = [vp, C.c_int, _ip64, _ip64]
+    lib.tpsrhs_lattice_coordinates.argtypes = [vp, C.c_int, vp]
+    lib.tpsrhs_lattice_fields.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int]
     lib.tpsrhs_transfer_stats.argtypes = [vp, _ip64, _ip64]
     lib.tpsrhs_probe_configure.argtypes = [vp, vp, C.c_int64, C.c_int64]
     lib.tpsrhs_probe_read.argtypes = [vp, _ip64, _ip64, vp, vp, vp, C.c_int]
@@ -865,6 +868,7 @@ EXPORTED_SYMBOLS = [
     "tpsrhs_locate_points", "tpsrhs_plane_points", "tpsrhs_sampler_create", "tpsrhs_sampler_destroy", "tpsrhs_sampler_info",
     "tpsrhs_sample", "tpsrhs_probe_configure", "tpsrhs_probe_read",
     "tpsrhs_sampler_create_device", "tpsrhs_node_coordinates", "tpsrhs_transfer", "tpsrhs_transfer_stats",
+    "tpsrhs_lattice_size", "tpsrhs_lattice_coordinates", "tpsrhs_lattice_fields",
     "tpsrhs_wall_faces", "tpsrhs_wall_distance",
     "tpsrhs_quadrature_points", "tpsrhs_integrate", "tpsrhs_nodal_stats", "tpsrhs_monitor_configure", "tpsrhs_monitor_read",
     "tpsrhs_patch_faces", "tpsrhs_surface_create", "tpsrhs_surface_destroy", "tpsrhs_surface_info", "tpsrhs_surface_integrate",

@@ -318,6 +318,43 @@ class RHSoperator:
             raise TpsRhsError(st, "tpsrhs_node_coordinates")
         return out
 
+    # -- fields on a refined element lattice: what a ParaView output step evaluates ---------------------------------------
+    def latticeSize(self, levels: int):
+        """``(points_per_element, npts)`` of the closed uniform lattice with ``levels`` intervals per direction
+        (``tpsrhs_lattice_size``): ``(levels + 1)^dim`` and that times the element count.  Host only."""
+        ppe, npts = C.c_int64(0), C.c_int64(0)
+        st = self._lib.tpsrhs_lattice_size(self._h, int(levels), C.byref(ppe), C.byref(npts))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_lattice_size")
+        return ppe.value, npts.value
+
+    def latticeCoordinates(self, levels: int) -> torch.Tensor:
+        """Physical coordinates of the lattice points, a new CUDA tensor ``(dim, npts)`` (``tpsrhs_lattice_coordinates``);
+        point ``e * (levels + 1)^dim + a + b (levels + 1) + c (levels + 1)^2``.  A corner is the element's vertex bit for
+        bit.  Asynchronous on the operator's stream."""
+        _, npts = self.latticeSize(levels)
+        out = torch.empty((self.dim, npts), dtype=torch.float64, device=self.device)
+        st = self._lib.tpsrhs_lattice_coordinates(self._h, int(levels), C.c_void_p(out.data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_lattice_coordinates")
+        return out
+
+    def latticeFields(self, field: torch.Tensor, levels: int, dtype=torch.float64) -> torch.Tensor:
+        """``field`` (a float64 CUDA tensor of ``nrows * NDofs`` entries, byNODES: ``[NDofs]`` or ``[nrows, NDofs]``) at the
+        lattice points of every element, each element with its own polynomial (``tpsrhs_lattice_fields``): a new CUDA
+        tensor ``(nrows, npts)`` of ``dtype`` float64, or float32 -- the double value rounded once.  Asynchronous on the
+        operator's stream."""
+        if dtype not in (torch.float64, torch.float32):
+            raise ValueError("dtype is torch.float64 or torch.float32")
+        nrows = self._rows(field)
+        _, npts = self.latticeSize(levels)
+        out = torch.empty((nrows, npts), dtype=dtype, device=field.device)
+        st = self._lib.tpsrhs_lattice_fields(self._h, int(levels), nrows, C.c_void_p(field.data_ptr()),
+                                             C.c_void_p(out.data_ptr()), 1 if dtype == torch.float32 else 0)
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_lattice_fields")
+        return out
+
     def transferFrom(self, src_op: "RHSoperator", field: torch.Tensor, tol: float = 0.0, fill: float = 0.0):
         """``field`` of ``src_op`` at the nodes of this operator (``tpsrhs_transfer``; ``utils/pfield_interpolate.cpp:138-146``
         and ``CycleAvgJouleCoupling``): ``field`` is a float64 CUDA tensor of ``nrows * src_op.NDofs`` entries (byNODES);
