@@ -1129,6 +1129,65 @@ int tpsrhs_lte_composition(tpsrhs_handle h, int64_t n, const double *T, const do
 int tpsrhs_species_from_lte(tpsrhs_handle h, const tpsrhs_lte_restart *tables, double *x, double *up_out,
                             tpsrhs_lte_restart_report *report);
 
+/* ---- conservative positivity limiter (a replacement for Check_Undershoot the reference does not have) -------------------
+ * After every step the reference sets negative species densities to zero (M2ulPhyS::Check_Undershoot,
+ * src/M2ulPhyS.cpp:2522-2548); its own comment names the remedy it lacks ("the effect of oscillations can be mitigated by
+ * employing a TVD scheme", :2522-2525).  That clamp adds mass with every firing.  This is the Zhang-Shu linear scaling
+ * limiter, element by element: it leaves every element mean, and so every tpsrhs_integrate total, where it was.  Opt-in:
+ * with no limiter configured nothing changes by a bit.  THE OPERATION, part of the contract:
+ *   Weights.  W_n = int_K l_n dV on THE RULE of tpsrhs_integrate: NQ = p + 2 Gauss-Legendre points per direction, order-1
+ *     geometry, the operator's Lagrange basis (Gauss-Legendre or Gauss-Lobatto nodes), |det J| at each point, times r_q
+ *     when the operator is axisymmetric.  So sum_n W_n f_n equals tpsrhs_integrate(f).sum up to rounding for both basis /
+ *     rule pairs; on the Gauss-Lobatto pair the W_n are NOT the nodal quadrature weights.  Computed once per operator on
+ *     the device (the transpose of tpsrhs_integrate's interpolation, sum-factorised), kept in a [NDofs] buffer the
+ *     operator owns, freed by tpsrhs_destroy.
+ *   Row step.  Element K with N nodes, a row v and a floor f:  mean = sum W_n v_n / sum W_n;  m = min_n v_n, kept with
+ *     `<`, so a NaN never wins.
+ *       1. mean is NaN: the element is left as it is and not counted (the NaN census of the loop reports it).
+ *       2. m >= f: untouched, nothing is written.
+ *       3. else mean > f: theta = (mean - f) / (mean - m);  v_n <- mean + theta (v_n - mean);  then v_n <- fmax(v_n, f),
+ *          which after the scaling can only move a value by rounding.  Counted in limited[row].
+ *       4. else the mean itself is inadmissible and no conservative fix exists: v_n <- fmax(v_n, f), the reference's clamp
+ *          for this element only.  Counted in clamped[row].
+ *   Pressure step.  Dry air only, after the row steps, only when pressure_floor = f_p > 0.
+ *     p(U) = (gamma - 1)(U[nvel+1] - 1/2 sum_{d=1..nvel} U[d]^2 / U[0]), gamma of tpsrhs_dry_air; Ubar the vector of the
+ *     element means of all rows; pbar = p(Ubar), p_min = min_n p(U_n).  p_min >= f_p: nothing happens.  Else pbar > f_p:
+ *     theta = (pbar - f_p) / (pbar - p_min), every row of the element is scaled as v_n <- vbar + theta (v_n - vbar);
+ *     counted in pressure_limited.  p is concave in U for rho > 0, so p(U_n') >= (1 - theta) pbar + theta p(U_n) >= f_p up
+ *     to rounding: no quadratic is solved.  Else the element is left untouched and counted in pressure_unfixable.
+ * In the time loop (tpsrhs_limiter_configure): one step is the stage sequence followed by the limiter, in tpsrhs_step,
+ * tpsrhs_rk4_step and every step of tpsrhs_advance / tpsrhs_advance_with (inside the captured step graph).  The limiter
+ * replaces the clamp on the rows it lists: it must list all species rows or none (the clamp range stays contiguous).  The
+ * statistics, probes, monitor and patch history see the limited state.  RK4 inside an advance runs unchained (x changes
+ * after stage 4: every step starts with its own k_traces sweep).  dt of the next step comes from the last stage's
+ * max_char_speed as without the limiter: the limiter does not feed it.  Element-local: partitioned meshes need nothing. */
+typedef struct tpsrhs_limiter { /* replaces Check_Undershoot, src/M2ulPhyS.cpp:2522-2548 */
+  int num_rows;                         /* -1: the rows Check_Undershoot clamps, [sp_first, sp_last) of the plan, floor 0 */
+  int rows[TPSRHS_MAXEQUATIONS];
+  double floors[TPSRHS_MAXEQUATIONS];
+  double pressure_floor;                /* 0: off; > 0: dry air only, needs row 0 listed with a floor > 0 */
+} tpsrhs_limiter;
+typedef struct tpsrhs_limiter_report { /* what took Check_Undershoot's place, src/M2ulPhyS.cpp:2522-2548 */
+  int64_t calls, limited[TPSRHS_MAXEQUATIONS], clamped[TPSRHS_MAXEQUATIONS], pressure_limited, pressure_unfixable;
+} tpsrhs_limiter_report;                /* limited / clamped indexed by state row */
+/* Refusals of the four entry points, all before any device work.  TPSRHS_ERR_INVALID_ARGUMENT: a NULL handle, x or out; a
+ * row outside [0, neq) or listed twice; num_rows < -1 or > neq; a NaN floor; pressure_floor < 0 or NaN; pressure_floor > 0
+ * without row 0 at a floor > 0; (configure only) some species rows listed but not all.  TPSRHS_ERR_UNSUPPORTED, with a
+ * message: pressure_floor > 0 on a mixture or the table gas.  num_rows = -1 on an operator without species rows (dry air,
+ * table gas) is a valid, empty limiter. */
+/* The weights W_n (src/M2ulPhyS.cpp:2522-2548 has no counterpart).  w_out: DEVICE [NDofs]; synchronous on return. */
+int tpsrhs_limiter_weights(tpsrhs_handle h, double *w_out /* DEVICE [NDofs] */);
+/* One application of `lim` to x (DEVICE [num_equation][NDofs], in place; in place of src/M2ulPhyS.cpp:2522-2548),
+ * asynchronous on the operator's stream.  Adds to the counters tpsrhs_limiter_read reports. */
+int tpsrhs_limit(tpsrhs_handle h, const tpsrhs_limiter *lim, double *x /* DEVICE, in place */);
+/* The limiter of the time loop (in place of the clamp of src/M2ulPhyS.cpp:2522-2548); NULL: off, the clamp is back.  A
+ * step graph captured before the call is not replayed. */
+int tpsrhs_limiter_configure(tpsrhs_handle h, const tpsrhs_limiter *lim /* NULL: off */);
+/* The counters since the operator was created or since the last read with reset != 0 (elements per outcome, where
+ * src/M2ulPhyS.cpp:2522-2548 counts nothing); calls: applications.  Integer sums: two runs give the same numbers.
+ * Synchronises the stream. */
+int tpsrhs_limiter_read(tpsrhs_handle h, tpsrhs_limiter_report *out, int reset);
+
 /* Host-only view of the face topology tpsrhs_create derives from a mesh (the role of the
  * indirection arrays of src/M2ulPhyS.cpp:816-1486); touches no device.  Outputs (caller-allocated):
  *   face_nbr[ne*2*dim]   >= 0: trace slot (element*2*dim + local face) of the neighbour, slots

@@ -160,6 +160,37 @@ class LteRestartReport(C.Structure):  # tpsrhs_lte_restart_report
                 ("t_min", C.c_double), ("t_max", C.c_double)]
 
 
+class Limiter(C.Structure):  # tpsrhs_limiter: num_rows = -1 selects the species rows Check_Undershoot clamps, floor 0
+    _fields_ = [("num_rows", C.c_int), ("rows", C.c_int * MAXEQUATIONS), ("floors", C.c_double * MAXEQUATIONS),
+                ("pressure_floor", C.c_double)]
+
+
+class LimiterReport(C.Structure):  # tpsrhs_limiter_report: elements per outcome, limited / clamped indexed by state row
+    _fields_ = [("calls", C.c_int64), ("limited", C.c_int64 * MAXEQUATIONS), ("clamped", C.c_int64 * MAXEQUATIONS),
+                ("pressure_limited", C.c_int64), ("pressure_unfixable", C.c_int64)]
+
+
+def make_limiter(rows=None, floors=None, pressure_floor=0.0) -> Limiter:
+    """``rows=None``: the species rows (``num_rows = -1``); ``floors``: one number for every row, or one per row (default 0)."""
+    lim = Limiter()
+    lim.pressure_floor = float(pressure_floor)
+    if rows is None:
+        lim.num_rows = -1
+        return lim
+    rows = [int(r) for r in rows]
+    if len(rows) > MAXEQUATIONS:
+        raise ValueError(f"at most {MAXEQUATIONS} rows")
+    if floors is None:
+        floors = 0.0
+    floors = [float(floors)] * len(rows) if np.isscalar(floors) else [float(f) for f in floors]
+    if len(floors) != len(rows):
+        raise ValueError("one floor per row")
+    lim.num_rows = len(rows)
+    for i, (r, f) in enumerate(zip(rows, floors)):
+        lim.rows[i], lim.floors[i] = r, f
+    return lim
+
+
 class VisLayout(C.Structure):  # tpsrhs_vis_layout: first ROW of each group of tpsrhs_visualization_fields, -1 = absent
     _fields_ = [("nrows", C.c_int), ("Xsp", C.c_int), ("Ysp", C.c_int), ("nsp_", C.c_int), ("FluxTrns", C.c_int),
                 ("diffVel", C.c_int), ("SrcTrns", C.c_int), ("SpeciesTrns", C.c_int), ("rxn", C.c_int),
@@ -827,6 +858,10 @@ def load():
     lib.tpsrhs_nodal_stats.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     lib.tpsrhs_monitor_configure.argtypes = [vp, C.c_int64, C.c_int64]
     lib.tpsrhs_monitor_read.argtypes = [vp, _ip64, _ip64, vp, vp, vp, vp, vp, vp, C.c_int]
+    lib.tpsrhs_limiter_weights.argtypes = [vp, vp]
+    lib.tpsrhs_limit.argtypes = [vp, C.POINTER(Limiter), vp]
+    lib.tpsrhs_limiter_configure.argtypes = [vp, C.POINTER(Limiter)]
+    lib.tpsrhs_limiter_read.argtypes = [vp, C.POINTER(LimiterReport), C.c_int]
     lib.tpsrhs_patch_faces.argtypes = [C.POINTER(Mesh), C.c_int, vp, C.c_int64, vp, vp, vp, _ip64]
     lib.tpsrhs_surface_create.argtypes = [vp, C.c_int, C.c_int64, vp, vp, vp, C.POINTER(vp)]
     lib.tpsrhs_surface_destroy.argtypes = [vp]
@@ -877,6 +912,7 @@ EXPORTED_SYMBOLS = [
     "tpsrhs_visualization_layout", "tpsrhs_visualization_fields",
     "tpsrhs_set_reaction_rates", "tpsrhs_boltzmann_fields",
     "tpsrhs_lte_composition", "tpsrhs_species_from_lte",
+    "tpsrhs_limiter_weights", "tpsrhs_limit", "tpsrhs_limiter_configure", "tpsrhs_limiter_read",
 ]
 
 

@@ -40,6 +40,11 @@ void monitor_record(tpsrhs_operator *h, const double *x);
 tpsrhs::StepCadence *surface_cadence(tpsrhs_operator *h);  // surface.hip
 void surface_record(tpsrhs_operator *h, const double *x);
 
+// ---- limiter.hip: the conservative limiter the time loop applies after the stages of every step (limiter.hpp)
+bool limiter_active(const tpsrhs_operator *h);          // tpsrhs_limiter_configure has set one
+bool limiter_replaces_clamp(const tpsrhs_operator *h);  // ... which lists the species rows: the stages' clamp range is empty
+void limiter_apply(tpsrhs_operator *h, double *x);      // k_limit on the operator's stream; needs limiter_active
+
 // ---- sampling.hip
 // h is being destroyed: tpsrhs_transfer forgets it as a source and drops every cached sampler at its nodes (the cache is
 // keyed by the address of the destination, which the next tpsrhs_create may hand out again)

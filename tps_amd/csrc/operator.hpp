@@ -34,6 +34,7 @@ struct tpsrhs_stats_state;      // statistics.hpp: running mean and velocity cov
 struct tpsrhs_sampling_state;   // sampling.hpp: point samplers and probe records (sampling.hip)
 struct tpsrhs_integrals_state;  // integrals.hpp: reduction scratch and monitor records (integrals.hip)
 struct tpsrhs_surface_state;    // surface.hpp: face sets of boundary patches and their history (surface.hip)
+struct tpsrhs_limiter_state;    // limiter.hip: weights, counters and the configured limiter of the time loop
 // The owner of one of them: its type is complete in the one unit that creates it, which hands the deleter over with it
 // (this struct's inline destructor is compiled in every unit, the kernel families included).
 template <class T>
@@ -148,7 +149,7 @@ struct tpsrhs_operator {
     DevBuf<double> d_ctl;              // {dt, time, max speed}: loop_ctl allocates, advance_with and k_step_end write
     StepGraph graph;                   // advance_with, through ensure
     TraceChain chain;                  // launch_all asks mult(); rk4_stages, rk_stages and advance_with make the transitions
-    int config_epoch = 0;              // bumped by whatever changes what a step launches: the forcing and mixing-length setters
+    int config_epoch = 0;              // bumped by whatever changes what a step launches: the forcing, mixing-length and limiter setters
     bool sweep_alt = true;             // alternate the direction of consecutive sweeps (launch_all); setup, TPSRHS_SWEEP_ALT
     int sweep_parity = 0;              // launch_all flips it once per Mult
   } loop;
@@ -210,6 +211,7 @@ struct tpsrhs_operator {
     sampling.reset();
     integrals.reset();
     surface.reset();
+    limiter.reset();
     for (auto &e : ev_halo)
       if (e) (void)hipEventDestroy(e);
     if (comm_stream) (void)hipStreamDestroy(comm_stream);
@@ -218,9 +220,13 @@ struct tpsrhs_operator {
         if (e) (void)hipEventDestroy(e);
   }
   // tpsrhs_get_flux (flux_fields.hpp): the pass of a plasma family, set with vis_fields from the same shared object; NULL for
-  // every other physics, whose passes live in flux_fields.hip.  (part, x, out) on the operator's stream.  Last member: the
-  // layout of everything before it is what the units of the sweeps were compiled with.
+  // every other physics, whose passes live in flux_fields.hip.  (part, x, out) on the operator's stream.  (It was
+  // appended when the units of the sweeps could be older than the core; a full build compiles every unit against this header,
+  // so the order of the members means nothing: state that comes later is appended below.)
   void (*flux_fields)(tpsrhs_operator *, int, const double *, double *) = nullptr;
+  // tpsrhs_limiter_weights / tpsrhs_limit / tpsrhs_limiter_configure (limiter.hip): the weights W_n, the counters and the
+  // limiter the time loop applies after every step; NULL: none yet.  Reset with the other states in the destructor.
+  OwnedState<tpsrhs_limiter_state> limiter{nullptr, nullptr};
 };
 
 #endif

@@ -33,7 +33,8 @@ void rk4_stages(tpsrhs_operator *h, double *x, double dt, const double *dt_dev) 
   TraceChain &chain = h->loop.chain;
   chain.begin_step();
   ScopeExit step([&](bool) { chain.end_step(); });
-  const int sp_first = h->loop.sp_first, sp_last = h->loop.sp_last;
+  // Check_Undershoot's rows; none when the limiter has taken them over (limiter.hpp)
+  const int sp_first = h->loop.sp_first, sp_last = limiter_replaces_clamp(h) ? sp_first : h->loop.sp_last;
   const int grid = static_cast<int>(std::min<int64_t>((n + 255) / 256, 8192));
   if (!h->forcing_active) {
     // The stage combinations in k_flux's epilogue (RkDev, kernel_args.hpp): k never goes to memory, the accumulator of
@@ -98,8 +99,8 @@ void rk_stages(tpsrhs_operator *h, int integrator, double *x, double dt, const d
   double *k = sc.k, *y = sc.y;
   h->loop.chain.begin_step();  // every Mult of these schemes runs its own k_traces sweep
   ScopeExit step([h](bool) { h->loop.chain.end_step(); });
-  // Check_Undershoot's rows, contiguous in [neq][ndofs]
-  const int64_t lo = h->loop.sp_first * h->ndofs, hi = h->loop.sp_last * h->ndofs;
+  // Check_Undershoot's rows, contiguous in [neq][ndofs]; none when the limiter has taken them over (limiter.hpp)
+  const int64_t lo = h->loop.sp_first * h->ndofs, hi = limiter_replaces_clamp(h) ? lo : h->loop.sp_last * h->ndofs;
   h->launch(h, x, k, false);  // k = f(x); SetTime is a no-op for this operator
   if (integrator == TPSRHS_FORWARD_EULER) {
     rk_stage<RK_EULER>(h, n, lo, hi, dt, dt_dev, x, k, y);
@@ -132,11 +133,14 @@ int check_integrator(int integrator, const char *who) {
   }
 }
 
+// One step: the stage sequence, then the limiter when one is configured (k_limit, the last launch that writes x: the
+// observers and the next step see the limited state; the step size of the next step still comes from the last stage).
 void step_stages(tpsrhs_operator *h, int integrator, double *x, double dt, const double *dt_dev) {
   if (integrator == TPSRHS_RK4)
     rk4_stages(h, x, dt, dt_dev);
   else
     rk_stages(h, integrator, x, dt, dt_dev);
+  if (limiter_active(h)) limiter_apply(h, x);
 }
 
 // What the time loop does between two steps, and whether any of it falls after the first of the next two: everything that
@@ -216,7 +220,8 @@ int advance_with(tpsrhs_handle h, int integrator, const char *who, double *x, do
     {
       // the session: the boundary conditions read dt from device memory, the steps are chained; put back however it ends
       h->nr_dt_dev = d_ctl;
-      h->loop.chain.begin_advance(integrator == TPSRHS_RK4 && !h->forcing_active);
+      // (a limiter rewrites x after stage 4: the traces stage 4 would leave for the next step would be stale)
+      h->loop.chain.begin_advance(integrator == TPSRHS_RK4 && !h->forcing_active && !limiter_active(h));
       ScopeExit session([&](bool) {
         h->nr_dt_dev = nullptr;
         h->loop.chain.end_advance();

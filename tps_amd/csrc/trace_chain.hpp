@@ -16,8 +16,12 @@
 //
 // Why StepKey = (x, constant_dt, bstate_cur, config_epoch, integrator, cfl hmin / dim) is enough to decide a replay -- what
 // else could change what a replayed step launches, and why it cannot:
-//   - chained is (RK4 and no forcing), and forcing changes only in tpsrhs_set_forcing / tpsrhs_set_joule_heating, which
-//     bump config_epoch.
+//   - chained is (RK4 and no forcing and no limiter), and forcing changes only in tpsrhs_set_forcing /
+//     tpsrhs_set_joule_heating, which bump config_epoch.
+//   - the limiter (limiter.hip): a configured limiter makes the last launch of a step k_limit, which rewrites x after stage
+//     4 -- the traces stage 4 would leave for the next step would be stale, so the advance is not chained, the rule stated
+//     for forcing terms.  Whether it runs, its rows and floors (kernel arguments by value) and the clamp range of the stage
+//     kernels change only in tpsrhs_limiter_configure, which bumps config_epoch.
 //   - validity and the buffers: the first step of every advance runs outside the graph, after begin_advance (a k_traces
 //     sweep of its own), and the even number of swaps above does the rest.  Fusing is fixed when the operator is created.
 //   - sweep_parity: only the order in which the workgroups walk the block list.  Every element's outputs depend on the
@@ -69,8 +73,8 @@ class TraceChain {
     if (!chained_) valid_ = false;
   }
   void end_step() { begin_step(); }
-  // chained: RK4 without forcing terms (with them the stage kernel runs and nothing is fused; the other integrators
-  // never enter the chain)
+  // chained: RK4 without forcing terms and without a limiter (with forcing the stage kernel runs and nothing is fused; a
+  // limiter rewrites x after stage 4; the other integrators never enter the chain)
   void begin_advance(bool chained) {
     valid_ = false;
     chained_ = chained;

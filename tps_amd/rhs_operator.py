@@ -603,6 +603,50 @@ class RHSoperator:
         return dict(iters=iters[:n].copy(), times=times[:n].copy(), dts=dts[:n].copy(), totals=totals[:n].copy(),
                     mins=mins[:n].copy(), maxs=maxs[:n].copy(), ndropped=ndrop.value)
 
+    # -- the conservative positivity limiter (in place of Check_Undershoot's clamp, src/M2ulPhyS.cpp:2522-2548) --------------
+    def limiterWeights(self) -> torch.Tensor:
+        """``W_n = int_K l_n dV`` on the rule of :meth:`integrate` (with the radial factor when the operator is
+        axisymmetric), a new CUDA tensor ``(NDofs,)``: ``(W * f).sum()`` is ``integrate(f)[0]`` up to rounding."""
+        out = torch.empty(self.NDofs, dtype=torch.float64, device=self.device)
+        st = self._lib.tpsrhs_limiter_weights(self._h, C.c_void_p(out.data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_limiter_weights")
+        return out
+
+    def limit(self, x: torch.Tensor, rows=None, floors=None, pressure_floor: float = 0.0):
+        """One application of the Zhang-Shu linear scaling limiter to ``x`` in place, element by element: every listed
+        row ends ``>= floor`` and every element mean stays where it was (``include/tpsrhs.h`` states the operation).
+        ``rows=None``: the species rows ``Check_Undershoot`` clamps, floor 0; ``floors``: one number or one per row;
+        ``pressure_floor > 0`` (dry air, row 0 listed with a floor > 0) adds the pressure step.  Asynchronous on the
+        operator's stream; adds to the counters of :meth:`readLimiter`."""
+        self._check(x)
+        lim = capi.make_limiter(rows, floors, pressure_floor)
+        st = self._lib.tpsrhs_limit(self._h, C.byref(lim), C.c_void_p(x.data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_limit")
+
+    def configureLimiter(self, rows=None, floors=None, pressure_floor: float = 0.0, off: bool = False):
+        """The limiter of the time loop: :meth:`step`, :meth:`rk4_step` and every step of :meth:`advance` end with one
+        application (arguments as in :meth:`limit`), which takes the place of the species clamp on the rows it lists
+        (all species rows or none).  The statistics, probes and monitor see the limited state.  ``off=True`` switches it
+        off and the clamp is back."""
+        lim = None if off else capi.make_limiter(rows, floors, pressure_floor)
+        st = self._lib.tpsrhs_limiter_configure(self._h, C.byref(lim) if lim is not None else None)
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_limiter_configure")
+
+    def readLimiter(self, reset: bool = False):
+        """``dict(calls, limited (num_equation,), clamped (num_equation,), pressure_limited, pressure_unfixable)``: the
+        applications and the elements per outcome and state row since the last reset; synchronises."""
+        rep = capi.LimiterReport()
+        st = self._lib.tpsrhs_limiter_read(self._h, C.byref(rep), 1 if reset else 0)
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_limiter_read")
+        neq = self.num_equation
+        return dict(calls=rep.calls, limited=np.array(rep.limited[:neq], dtype=np.int64),
+                    clamped=np.array(rep.clamped[:neq], dtype=np.int64), pressure_limited=rep.pressure_limited,
+                    pressure_unfixable=rep.pressure_unfixable)
+
     # -- surface integrals over boundary patches and their history -----------------------------------------------------------
     def createSurface(self, attributes=None, faces=None) -> "Surface":
         """A set of element faces in patches (``tpsrhs_surface_create``).  ``attributes``: the boundary attributes of the
