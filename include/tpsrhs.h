@@ -1188,6 +1188,66 @@ int tpsrhs_limiter_configure(tpsrhs_handle h, const tpsrhs_limiter *lim /* NULL:
  * Synchronises the stream. */
 int tpsrhs_limiter_read(tpsrhs_handle h, tpsrhs_limiter_report *out, int reset);
 
+/* ---- Legendre modal filter and smoothness sensor (the compressible solver of the reference has neither) ------------------
+ * The exponential modal filter of Hesthaven & Warburton takes out the energy that piles up in the highest modes of an
+ * under-resolved nodal DG solution before it becomes the undershoot the limiter above has to repair; the modal-decay sensor
+ * of Persson & Peraire says, per element, where the solution is under-resolved.  Both are one small tensor contraction per
+ * element, element-local (partitioned meshes need nothing), and do not look at the physics: every order 1 .. 5, both basis
+ * / rule pairs, quads, hexes and axisymmetric operators, every gas model.  Opt-in: with no filter configured nothing
+ * changes by a bit.  THE OPERATION, part of the contract, per element with N1 = p + 1 nodes per direction, xi_a in [0, 1]
+ * the operator's own nodes (Gauss-Legendre or Gauss-Lobatto), lexicographic node order as everywhere:
+ *   Modes.  V[a][k] = P_k(2 xi_a - 1), the Legendre polynomials, k = 0 .. p.  The modal coefficients of a nodal row u are
+ *     u^ = (V^-1 x ... x V^-1) u, V^-1 along each of the dim directions.  V, V^-1 and F are formed on the host from the
+ *     order and the basis, rounded to double, and go to the kernels by value.
+ *   Filter.  sigma_k = 1 for k <= k_c = cutoff, sigma_k = exp(-alpha ((k - k_c) / (p - k_c))^s) for k > k_c, s = exponent.
+ *     F = V diag(sigma) V^-1 and u~ = (F x ... x F) u.  With conservative != 0, afterwards
+ *     u~_n += sum_n W_n (u_n - u~_n) / sum_n W_n with W_n the weights of tpsrhs_limiter_weights (the rule of
+ *     tpsrhs_integrate, times r when the operator is axisymmetric): every element integral, and so every tpsrhs_integrate
+ *     total, stays where it was on any mesh.  With conservative == 0 only the reference-space mean is kept (sigma_0 = 1),
+ *     which is the physical mean on affine elements only.
+ *   Shell energies and sensor of one scalar field.  gamma_k = 1 / (2k + 1);
+ *     E_m = sum over the modes with max(i, j[, k]) = m of u^^2 gamma_i gamma_j [gamma_k], m = 0 .. p: the reference-space L2
+ *     norm squared, split by the highest 1-D degree.  S = E_p / sum_m E_m; S = 0 when the sum is 0; S is NaN when the
+ *     element holds a NaN.
+ *   Selective filtering.  With sensor_row >= 0, S is computed from that row of the INCOMING state, before any row is
+ *     written, and the element is filtered on all listed rows only if S > sensor_threshold (a NaN sensor: not filtered;
+ *     sensor_threshold = +inf: never).  With sensor_row = -1 every element is filtered.  An element that is not filtered
+ *     is not written.
+ * In the time loop (tpsrhs_modal_filter_configure): one step is the stage sequence, then the filter, then the limiter when
+ * one is configured, in tpsrhs_step, tpsrhs_rk4_step and every step of tpsrhs_advance / tpsrhs_advance_with (inside the
+ * captured step graph).  The species clamp of the stage kernels runs BEFORE the filter, so a filter on species rows can
+ * undershoot again: the limiter, which has the last word on the floors, is the remedy.  The statistics, probes, monitor
+ * and patch history see the filtered (then limited) state.  RK4 inside an advance runs unchained, as with a limiter (x
+ * changes after stage 4).  dt of the next step comes from the last stage's max_char_speed: the filter does not feed it. */
+typedef struct tpsrhs_modal_filter {
+  int num_rows;                       /* -1: every state row */
+  int rows[TPSRHS_MAXEQUATIONS];
+  int cutoff;                         /* k_c, 0 .. p-1 */
+  double alpha;                       /* > 0, finite */
+  int exponent;                       /* s >= 1 */
+  int conservative;
+  int sensor_row;                     /* -1: none */
+  double sensor_threshold;
+} tpsrhs_modal_filter;
+typedef struct tpsrhs_modal_filter_report { int64_t calls, elements_seen, elements_filtered; } tpsrhs_modal_filter_report;
+/* Refusals of the five entry points, all before any device work, TPSRHS_ERR_INVALID_ARGUMENT: a NULL handle, pointer or
+ * struct; a row outside [0, neq) or listed twice; num_rows < -1 or > neq; cutoff outside 0 .. p-1; alpha <= 0, NaN or inf;
+ * exponent < 1; sensor_row outside [-1, neq); a NaN threshold; nrows < 1; both outputs of tpsrhs_modal_energy NULL. */
+/* out = (V^-1 x ... x V^-1) in (inverse == 0) or (V x ... x V) in (inverse != 0), row by row.  in, out: DEVICE
+ * [nrows][NDofs]; in == out is allowed (otherwise they must not overlap).  Asynchronous on the operator's stream. */
+int tpsrhs_modal_transform(tpsrhs_handle h, int inverse, int nrows, const double *in, double *out);
+/* The shell energies and the sensor of one scalar field (DEVICE [NDofs]).  energy_out: DEVICE [ne][p+1] or NULL;
+ * sensor_out: DEVICE [ne] or NULL; not both NULL.  Asynchronous on the operator's stream. */
+int tpsrhs_modal_energy(tpsrhs_handle h, const double *field, double *energy_out, double *sensor_out);
+/* One application of `f` to x (DEVICE [num_equation][NDofs], in place), one kernel launch, asynchronous on the operator's
+ * stream.  Adds to the counters tpsrhs_modal_filter_read reports. */
+int tpsrhs_modal_filter_apply(tpsrhs_handle h, const tpsrhs_modal_filter *f, double *x);
+/* The filter of the time loop; NULL: off.  A step graph captured before the call is not replayed. */
+int tpsrhs_modal_filter_configure(tpsrhs_handle h, const tpsrhs_modal_filter *f /* NULL: off */);
+/* The counters since the operator was created or since the last read with reset != 0: applications, elements looked at,
+ * elements filtered.  Integer sums: two runs give the same numbers.  Synchronises the stream. */
+int tpsrhs_modal_filter_read(tpsrhs_handle h, tpsrhs_modal_filter_report *out, int reset);
+
 /* Host-only view of the face topology tpsrhs_create derives from a mesh (the role of the
  * indirection arrays of src/M2ulPhyS.cpp:816-1486); touches no device.  Outputs (caller-allocated):
  *   face_nbr[ne*2*dim]   >= 0: trace slot (element*2*dim + local face) of the neighbour, slots

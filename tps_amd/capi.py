@@ -191,6 +191,35 @@ def make_limiter(rows=None, floors=None, pressure_floor=0.0) -> Limiter:
     return lim
 
 
+class ModalFilter(C.Structure):  # tpsrhs_modal_filter: num_rows = -1 selects every state row, sensor_row = -1 no sensor
+    _fields_ = [("num_rows", C.c_int), ("rows", C.c_int * MAXEQUATIONS), ("cutoff", C.c_int), ("alpha", C.c_double),
+                ("exponent", C.c_int), ("conservative", C.c_int), ("sensor_row", C.c_int), ("sensor_threshold", C.c_double)]
+
+
+class ModalFilterReport(C.Structure):  # tpsrhs_modal_filter_report
+    _fields_ = [("calls", C.c_int64), ("elements_seen", C.c_int64), ("elements_filtered", C.c_int64)]
+
+
+def make_modal_filter(rows=None, cutoff=0, alpha=36.0, exponent=16, conservative=True, sensor_row=-1,
+                      sensor_threshold=0.0) -> ModalFilter:
+    """``rows=None``: every state row (``num_rows = -1``).  The defaults are the exponential filter of Hesthaven & Warburton
+    at machine-precision damping of the last mode (``alpha = 36``, ``s = 16``), mean-corrected, on every element."""
+    f = ModalFilter()
+    f.cutoff, f.alpha, f.exponent = int(cutoff), float(alpha), int(exponent)
+    f.conservative = 1 if conservative else 0
+    f.sensor_row, f.sensor_threshold = int(sensor_row), float(sensor_threshold)
+    if rows is None:
+        f.num_rows = -1
+        return f
+    rows = [int(r) for r in rows]
+    if len(rows) > MAXEQUATIONS:
+        raise ValueError(f"at most {MAXEQUATIONS} rows")
+    f.num_rows = len(rows)
+    for i, r in enumerate(rows):
+        f.rows[i] = r
+    return f
+
+
 class VisLayout(C.Structure):  # tpsrhs_vis_layout: first ROW of each group of tpsrhs_visualization_fields, -1 = absent
     _fields_ = [("nrows", C.c_int), ("Xsp", C.c_int), ("Ysp", C.c_int), ("nsp_", C.c_int), ("FluxTrns", C.c_int),
                 ("diffVel", C.c_int), ("SrcTrns", C.c_int), ("SpeciesTrns", C.c_int), ("rxn", C.c_int),
@@ -862,6 +891,11 @@ def load():
     lib.tpsrhs_limit.argtypes = [vp, C.POINTER(Limiter), vp]
     lib.tpsrhs_limiter_configure.argtypes = [vp, C.POINTER(Limiter)]
     lib.tpsrhs_limiter_read.argtypes = [vp, C.POINTER(LimiterReport), C.c_int]
+    lib.tpsrhs_modal_transform.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+    lib.tpsrhs_modal_energy.argtypes = [vp, vp, vp, vp]
+    lib.tpsrhs_modal_filter_apply.argtypes = [vp, C.POINTER(ModalFilter), vp]
+    lib.tpsrhs_modal_filter_configure.argtypes = [vp, C.POINTER(ModalFilter)]
+    lib.tpsrhs_modal_filter_read.argtypes = [vp, C.POINTER(ModalFilterReport), C.c_int]
     lib.tpsrhs_patch_faces.argtypes = [C.POINTER(Mesh), C.c_int, vp, C.c_int64, vp, vp, vp, _ip64]
     lib.tpsrhs_surface_create.argtypes = [vp, C.c_int, C.c_int64, vp, vp, vp, C.POINTER(vp)]
     lib.tpsrhs_surface_destroy.argtypes = [vp]
@@ -913,6 +947,8 @@ EXPORTED_SYMBOLS = [
     "tpsrhs_set_reaction_rates", "tpsrhs_boltzmann_fields",
     "tpsrhs_lte_composition", "tpsrhs_species_from_lte",
     "tpsrhs_limiter_weights", "tpsrhs_limit", "tpsrhs_limiter_configure", "tpsrhs_limiter_read",
+    "tpsrhs_modal_transform", "tpsrhs_modal_energy", "tpsrhs_modal_filter_apply", "tpsrhs_modal_filter_configure",
+    "tpsrhs_modal_filter_read",
 ]
 
 

@@ -44,6 +44,12 @@ void surface_record(tpsrhs_operator *h, const double *x);
 bool limiter_active(const tpsrhs_operator *h);          // tpsrhs_limiter_configure has set one
 bool limiter_replaces_clamp(const tpsrhs_operator *h);  // ... which lists the species rows: the stages' clamp range is empty
 void limiter_apply(tpsrhs_operator *h, double *x);      // k_limit on the operator's stream; needs limiter_active
+// the weights W_n (DEVICE [NDofs]) the operator owns, computed at the first use: the modal filter's mean correction reads them
+const double *limiter_weights_device(tpsrhs_operator *h);
+
+// ---- modal.hip: the modal filter the time loop applies after the stages of every step, before the limiter (modal.hpp)
+bool modal_filter_active(const tpsrhs_operator *h);       // tpsrhs_modal_filter_configure has set one
+void modal_filter_apply(tpsrhs_operator *h, double *x);   // k_modal_filter on the operator's stream; needs modal_filter_active
 
 // ---- sampling.hip
 // h is being destroyed: tpsrhs_transfer forgets it as a source and drops every cached sampler at its nodes (the cache is

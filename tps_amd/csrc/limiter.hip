@@ -285,6 +285,7 @@ void apply(tpsrhs_operator *h, const tpsrhs_limiter_state *ls, const LimiterPlan
 bool limiter_active(const tpsrhs_operator *h) { return h->limiter && h->limiter->active; }
 bool limiter_replaces_clamp(const tpsrhs_operator *h) { return limiter_active(h) && h->limiter->plan.covers_species; }
 void limiter_apply(tpsrhs_operator *h, double *x) { apply(h, h->limiter.get(), h->limiter->plan, x); }
+const double *limiter_weights_device(tpsrhs_operator *h) { return limiter_of(h)->d_w.get(); }
 
 extern "C" {
 

@@ -35,6 +35,7 @@ struct tpsrhs_sampling_state;   // sampling.hpp: point samplers and probe record
 struct tpsrhs_integrals_state;  // integrals.hpp: reduction scratch and monitor records (integrals.hip)
 struct tpsrhs_surface_state;    // surface.hpp: face sets of boundary patches and their history (surface.hip)
 struct tpsrhs_limiter_state;    // limiter.hip: weights, counters and the configured limiter of the time loop
+struct tpsrhs_modal_state;      // modal.hip: counters and the configured modal filter of the time loop
 // The owner of one of them: its type is complete in the one unit that creates it, which hands the deleter over with it
 // (this struct's inline destructor is compiled in every unit, the kernel families included).
 template <class T>
@@ -149,7 +150,7 @@ struct tpsrhs_operator {
     DevBuf<double> d_ctl;              // {dt, time, max speed}: loop_ctl allocates, advance_with and k_step_end write
     StepGraph graph;                   // advance_with, through ensure
     TraceChain chain;                  // launch_all asks mult(); rk4_stages, rk_stages and advance_with make the transitions
-    int config_epoch = 0;              // bumped by whatever changes what a step launches: the forcing, mixing-length and limiter setters
+    int config_epoch = 0;              // bumped by whatever changes what a step launches: the forcing, mixing-length, limiter and modal-filter setters
     bool sweep_alt = true;             // alternate the direction of consecutive sweeps (launch_all); setup, TPSRHS_SWEEP_ALT
     int sweep_parity = 0;              // launch_all flips it once per Mult
   } loop;
@@ -212,6 +213,7 @@ struct tpsrhs_operator {
     integrals.reset();
     surface.reset();
     limiter.reset();
+    modal.reset();
     for (auto &e : ev_halo)
       if (e) (void)hipEventDestroy(e);
     if (comm_stream) (void)hipStreamDestroy(comm_stream);
@@ -227,6 +229,9 @@ struct tpsrhs_operator {
   // tpsrhs_limiter_weights / tpsrhs_limit / tpsrhs_limiter_configure (limiter.hip): the weights W_n, the counters and the
   // limiter the time loop applies after every step; NULL: none yet.  Reset with the other states in the destructor.
   OwnedState<tpsrhs_limiter_state> limiter{nullptr, nullptr};
+  // tpsrhs_modal_filter_apply / tpsrhs_modal_filter_configure / tpsrhs_modal_filter_read (modal.hip): the counters and the
+  // filter the time loop applies after the stages of every step, before the limiter; NULL: none yet.
+  OwnedState<tpsrhs_modal_state> modal{nullptr, nullptr};
 };
 
 #endif

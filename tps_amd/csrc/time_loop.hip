@@ -133,13 +133,15 @@ int check_integrator(int integrator, const char *who) {
   }
 }
 
-// One step: the stage sequence, then the limiter when one is configured (k_limit, the last launch that writes x: the
-// observers and the next step see the limited state; the step size of the next step still comes from the last stage).
+// One step: the stage sequence, then the modal filter when one is configured (k_modal_filter), then the limiter when one
+// is configured (k_limit, the last launch that writes x and the last word on the floors: the observers and the next step
+// see the filtered, then limited state; the step size of the next step still comes from the last stage).
 void step_stages(tpsrhs_operator *h, int integrator, double *x, double dt, const double *dt_dev) {
   if (integrator == TPSRHS_RK4)
     rk4_stages(h, x, dt, dt_dev);
   else
     rk_stages(h, integrator, x, dt, dt_dev);
+  if (modal_filter_active(h)) modal_filter_apply(h, x);
   if (limiter_active(h)) limiter_apply(h, x);
 }
 
@@ -220,8 +222,8 @@ int advance_with(tpsrhs_handle h, int integrator, const char *who, double *x, do
     {
       // the session: the boundary conditions read dt from device memory, the steps are chained; put back however it ends
       h->nr_dt_dev = d_ctl;
-      // (a limiter rewrites x after stage 4: the traces stage 4 would leave for the next step would be stale)
-      h->loop.chain.begin_advance(integrator == TPSRHS_RK4 && !h->forcing_active && !limiter_active(h));
+      // (a limiter or a modal filter rewrites x after stage 4: the traces stage 4 would leave for the next step would be stale)
+      h->loop.chain.begin_advance(integrator == TPSRHS_RK4 && !h->forcing_active && !limiter_active(h) && !modal_filter_active(h));
       ScopeExit session([&](bool) {
         h->nr_dt_dev = nullptr;
         h->loop.chain.end_advance();

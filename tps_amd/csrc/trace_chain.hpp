@@ -16,8 +16,13 @@
 //
 // Why StepKey = (x, constant_dt, bstate_cur, config_epoch, integrator, cfl hmin / dim) is enough to decide a replay -- what
 // else could change what a replayed step launches, and why it cannot:
-//   - chained is (RK4 and no forcing and no limiter), and forcing changes only in tpsrhs_set_forcing /
+//   - chained is (RK4 and no forcing and no limiter and no modal filter), and forcing changes only in tpsrhs_set_forcing /
 //     tpsrhs_set_joule_heating, which bump config_epoch.
+//   - the modal filter (modal.hip): a configured filter adds one launch, k_modal_filter, after the stages and before
+//     k_limit; it rewrites x after stage 4, so the advance is not chained, by the rule and for the reason stated for the
+//     limiter below.  Whether it runs and everything it runs with (the matrix F, the rows, the sensor row and threshold,
+//     the conservative flag: kernel arguments by value; the weights: a buffer the operator owns for its lifetime) change
+//     only in tpsrhs_modal_filter_configure, which bumps config_epoch.  It leaves the clamp range of the stages alone.
 //   - the limiter (limiter.hip): a configured limiter makes the last launch of a step k_limit, which rewrites x after stage
 //     4 -- the traces stage 4 would leave for the next step would be stale, so the advance is not chained, the rule stated
 //     for forcing terms.  Whether it runs, its rows and floors (kernel arguments by value) and the clamp range of the stage
@@ -73,8 +78,8 @@ class TraceChain {
     if (!chained_) valid_ = false;
   }
   void end_step() { begin_step(); }
-  // chained: RK4 without forcing terms and without a limiter (with forcing the stage kernel runs and nothing is fused; a
-  // limiter rewrites x after stage 4; the other integrators never enter the chain)
+  // chained: RK4 without forcing terms, without a limiter and without a modal filter (with forcing the stage kernel runs
+  // and nothing is fused; a limiter or a filter rewrites x after stage 4; the other integrators never enter the chain)
   void begin_advance(bool chained) {
     valid_ = false;
     chained_ = chained;

@@ -647,6 +647,67 @@ class RHSoperator:
                     clamped=np.array(rep.clamped[:neq], dtype=np.int64), pressure_limited=rep.pressure_limited,
                     pressure_unfixable=rep.pressure_unfixable)
 
+    # -- Legendre modal filter and smoothness sensor -----------------------------------------------------------------------------
+    def _check_rows(self, t: torch.Tensor, what: str):
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.dim() in (1, 2) and t.shape[-1] == self.NDofs):
+            raise ValueError(f"{what}: a contiguous float64 CUDA tensor (NDofs,) or (nrows, NDofs)")
+
+    def modalTransform(self, field: torch.Tensor, inverse: bool = False) -> torch.Tensor:
+        """The Legendre modal coefficients ``(V^-1 x ... x V^-1) u`` of every row of ``field`` ``(NDofs,)`` or
+        ``(nrows, NDofs)``, element by element, in the node order of the element -- or, ``inverse=True``, the nodal values
+        of such coefficients.  A new CUDA tensor of the same shape; asynchronous on the operator's stream."""
+        self._check_rows(field, "modalTransform")
+        out = torch.empty_like(field)
+        nrows = 1 if field.dim() == 1 else field.shape[0]
+        st = self._lib.tpsrhs_modal_transform(self._h, 1 if inverse else 0, nrows, C.c_void_p(field.data_ptr()),
+                                              C.c_void_p(out.data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_modal_transform")
+        return out
+
+    def modalEnergy(self, field: torch.Tensor):
+        """``(energy (ne, p + 1), sensor (ne,))`` of one scalar field ``(NDofs,)``: the reference-space L2 norm squared of
+        every element split by the highest 1-D Legendre degree, and ``S = E_p / sum E`` (Persson & Peraire)."""
+        self._check_rows(field, "modalEnergy")
+        if field.dim() != 1:
+            raise ValueError("modalEnergy: one scalar field (NDofs,)")
+        ne = self.NDofs // (self._disc.order + 1) ** self.dim
+        energy = torch.empty((ne, self._disc.order + 1), dtype=torch.float64, device=self.device)
+        sensor = torch.empty(ne, dtype=torch.float64, device=self.device)
+        st = self._lib.tpsrhs_modal_energy(self._h, C.c_void_p(field.data_ptr()), C.c_void_p(energy.data_ptr()),
+                                           C.c_void_p(sensor.data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_modal_energy")
+        return energy, sensor
+
+    def modalFilter(self, x: torch.Tensor, **kw):
+        """One application of the exponential modal filter to ``x`` in place (``include/tpsrhs.h`` states the operation);
+        keywords as :func:`tps_amd.capi.make_modal_filter`: ``rows`` (default: every row), ``cutoff``, ``alpha``,
+        ``exponent``, ``conservative``, ``sensor_row``, ``sensor_threshold``.  Asynchronous on the operator's stream; adds
+        to the counters of :meth:`readModalFilter`."""
+        self._check(x)
+        f = capi.make_modal_filter(**kw)
+        st = self._lib.tpsrhs_modal_filter_apply(self._h, C.byref(f), C.c_void_p(x.data_ptr()))
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_modal_filter_apply")
+
+    def configureModalFilter(self, off: bool = False, **kw):
+        """The modal filter of the time loop: every step is the stage sequence, then one application of the filter
+        (keywords as in :meth:`modalFilter`), then the limiter when one is configured.  The statistics, probes and
+        monitor see the filtered state.  ``off=True`` switches it off."""
+        f = None if off else capi.make_modal_filter(**kw)
+        st = self._lib.tpsrhs_modal_filter_configure(self._h, C.byref(f) if f is not None else None)
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_modal_filter_configure")
+
+    def readModalFilter(self, reset: bool = False):
+        """``dict(calls, elements_seen, elements_filtered)`` since the last reset; synchronises."""
+        rep = capi.ModalFilterReport()
+        st = self._lib.tpsrhs_modal_filter_read(self._h, C.byref(rep), 1 if reset else 0)
+        if st != 0:
+            raise TpsRhsError(st, "tpsrhs_modal_filter_read")
+        return dict(calls=rep.calls, elements_seen=rep.elements_seen, elements_filtered=rep.elements_filtered)
+
     # -- surface integrals over boundary patches and their history -----------------------------------------------------------
     def createSurface(self, attributes=None, faces=None) -> "Surface":
         """A set of element faces in patches (``tpsrhs_surface_create``).  ``attributes``: the boundary attributes of the
